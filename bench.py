@@ -23,6 +23,11 @@ svo_exchange_frames (include/svo_rt.h), overlapped with the next step's cast on 
 Inputs (tree, camera) are resident in HBM before the timed region; the timed region is K steps
 between barrier + synchronize on both sides; the reported time is the max over ranks.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the
+line: the headline figure and the roofline object computed from the timed region itself.  --full adds the
+measurements that take runs of their own (N = 1: the CPU baseline with its C1 leg and parity check, the
+`pipelined` steps).  --dump-outputs DIR writes what the last timed step computed to DIR/<name>.npy.
+
 Extra objects on the JSON line:
   roofline     — the cast kernel's algorithmic bytes (B_ray = 16*E_node +
                  4*E_child + B_out per ray (+ the AO rays' entries for C4), E from profiles/bray.json)
@@ -32,9 +37,9 @@ Extra objects on the JSON line:
                  (`traffic`), measured HBM GB/s, L2 hit rate, VALU / SALU instructions per wave and
                  the VALU issue fraction; `bound` names the larger of the measured HBM and VALU-issue
                  fractions.
-  cpu_baseline — the oracle's C restatement of castRayFromCam + getBlock (reference node/array
-                 layout, full descent per step) timed on this host's cores on the same workload
-                 (rank 0, N=1), plus config C1 (dense grid) every time.
+  cpu_baseline — (--full; null otherwise) the oracle's C restatement of castRayFromCam + getBlock
+                 (reference node/array layout, full descent per step) timed on this host's cores on the
+                 same workload (rank 0, N=1), plus config C1 (dense grid) every time.
 """
 import argparse
 import collections
@@ -471,7 +476,15 @@ def main():
     ap.add_argument("--ao", type=int, default=0, help="config C4: hemisphere AO rays per primary hit (16 or 20)")
     ap.add_argument("--shade", action="store_true",
                     help="SURVEY §8f.1: shaded frames (svo_shade_rays: primary + reflections + 75-step sun shadow ray)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need (N = 1: the CPU baseline with its C1 leg and the "
+                         "parity check of the GPU frame, the `pipelined` steps); a plain run only sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (the arrays its caller receives: hit "
+                         "records, AO counts, the shaded image) as DIR/<name>.npy in float32 / float64, at most 64 MB in all "
+                         "(of a larger output: a fixed, seeded sample of the rays, listed in ray_index.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-c1", action="store_true", help="skip the C1 CPU timing inside cpu_baseline")
     ap.add_argument("--no-gather", action="store_true", help="N>1: cast only, no exchange")
     ap.add_argument("--exchange", default="capi", choices=["capi", "torch"],
@@ -492,13 +505,15 @@ def main():
     ap.add_argument("--pipelined-steps", type=int, default=None,
                     help="N = 1: after the timed region, time this many more steps with consecutive launches on two "
                          "alternating streams (a launch's tail overlaps the next one's head), reported as `pipelined` "
-                         "(default: --steps; 0: off)")
+                         "(default: --steps with --full, else 0; 0: off)")
     ap.add_argument("--launch-events", action="store_true",
                     help="an event pair around every cast launch (default at N=1: one pair around the timed region, whose "
                          "average per launch includes the gaps between launches; per-launch pairs cost ~7 us per step)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         # no launcher around us: start the ranks ourselves, before anything touches a GPU
@@ -604,7 +619,7 @@ def main():
     # tensors for the small control collectives: on the GPU over RCCL, on the host over gloo
     gdev = torch.device("cuda", dev)
     cdev = gdev if args.dist_backend == "nccl" else torch.device("cpu")
-    pipe_steps = args.steps if args.pipelined_steps is None else args.pipelined_steps
+    pipe_steps = (args.steps if args.full else 0) if args.pipelined_steps is None else args.pipelined_steps
     if gather or world > 1 or args.inflight > 1:
         pipe_steps = 0  # (an N = 1 measurement beside the contract's own)
     # the exchange (or the next launch) of step k overlaps step k+1.  With an exchange, three buffer sets: step k's
@@ -787,6 +802,19 @@ def main():
     total_rays = W * H * nframes * args.steps  # every rank's share of every frame, all steps
     value = total_rays / elapsed
     avg_kernel_s = float(np.mean(kern_ms)) / 1e3
+    if args.dump_outputs and rank == 0:
+        # the last timed step's buffers, before any later step reuses them: the displayed frames where an exchange
+        # assembled them, else what the cast / shading launch wrote
+        b = (step_no - 1) % nbuf
+        if gather and frames_out is not None:
+            got = frames_out
+        elif gather and tx is not None and tx.frames is not None:
+            got = tx.frames
+        elif args.shade:
+            got = {"rgba": outs[b]["rgba"]}
+        else:
+            got = outs[b]
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in got.items()})
     pipelined = None
     if pipe_steps:
         # the same steps with consecutive launches on two alternating streams: frames are independent, so a
@@ -853,7 +881,7 @@ def main():
     roof = roofline(args, cfg, rays_per_launch, avg_kernel_s, world, rt.lib_sha256())
     roof["timed_build"] = rt.lib_sha256()
     cpu = None
-    if world == 1 and nframes == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and nframes == 1 and not args.no_cpu_baseline:
         gpu = None
         if args.shade:
             gpu = {"rgba": outs[0]["rgba"].cpu().numpy()}
@@ -920,6 +948,38 @@ def main():
     print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together
+DUMP_SEED = 0
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: per-ray host arrays (first axis: the ray) -> path/<name>.npy.  float32 where every value is
+    exactly a float32 (floats as they are; integers below 2^24), else float64: no value changes.  When that would
+    pass DUMP_MAX_BYTES, the same seeded sample of the rays (DUMP_SEED) goes to every file, its sorted ray numbers
+    to ray_index.npy."""
+    conv = {}
+    for name, a in arrays.items():
+        if a.dtype == np.float32 or a.dtype == np.float64:
+            conv[name] = a
+        elif a.size == 0 or int(np.abs(a.astype(np.int64)).max()) < (1 << 24):
+            conv[name] = a.astype(np.float32)
+        else:
+            conv[name] = a.astype(np.float64)
+    n = len(next(iter(conv.values())))
+    per_ray = sum(a.dtype.itemsize * (a.size // max(1, n)) for a in conv.values())
+    budget = DUMP_MAX_BYTES - 4096 * (len(conv) + 1)  # (room for the files' headers)
+    idx = None
+    if n * per_ray > budget:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, budget // (per_ray + 8), replace=False))
+    os.makedirs(path, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a if idx is None else a[idx]))
+    if idx is not None:
+        np.save(os.path.join(path, "ray_index.npy"), idx.astype(np.float64))
+    elif os.path.exists(os.path.join(path, "ray_index.npy")):  # (an earlier, sampled dump's)
+        os.remove(os.path.join(path, "ray_index.npy"))
 
 
 def build_block(rt):

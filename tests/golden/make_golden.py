@@ -5,6 +5,8 @@ Sources (all reference-produced, none from this repo's code):
   * noise_ref.npz     — include/OpenSimplexNoise.cpp compiled from /root/reference by oracle/Makefile
                         (oracle/_ref/libref_noise.so): Noise(seed).eval(x, y) at world-gen sample
                         points and random points, seeds 42/64/100 (world_gen.cpp:15-17) + others.
+  * noise_live_ref.npz — the same library at seed 42 on the 5000 random points of
+                        test_noise_matches_compiled_reference_live, so that the test needs no reference sources.
   * hemisphere_ref.json — stdout of /root/reference/gen_hemisphare_distrib.py (N = 20, run with
                         MPLBACKEND=Agg), plus the 20 literals of src/shaders/light_scattering.frag:
                         134-153 as DATA (the float32 table the shader uses).
@@ -53,6 +55,17 @@ def noise():
     np.savez_compressed(os.path.join(HERE, "noise_ref.npz"), x=x, y=y, seed=s, value=v)
 
 
+def noise_live():
+    """noise_live_ref.npz: the points of tests/test_oracle_golden.py::test_noise_matches_compiled_reference_live
+    (5000 uniform in [-500, 500)^2, default_rng(7), seed 42) and the compiled reference's values at them"""
+    from oracle import oracle as O
+
+    O.build_ref()
+    rng = np.random.default_rng(7)
+    x, y = rng.uniform(-500, 500, 5000), rng.uniform(-500, 500, 5000)
+    np.savez_compressed(os.path.join(HERE, "noise_live_ref.npz"), x=x, y=y, value=O.ref_noise_batch(42, x, y))
+
+
 def hemisphere():
     env = dict(os.environ, MPLBACKEND="Agg")
     out = subprocess.run([sys.executable, os.path.join(REF, "gen_hemisphare_distrib.py")], capture_output=True, text=True,
@@ -90,6 +103,7 @@ def facts():
 
 if __name__ == "__main__":
     noise()
+    noise_live()
     hemisphere()
     facts()
     print("golden vectors written to", HERE)

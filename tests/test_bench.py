@@ -218,3 +218,32 @@ def test_watchdog_bound_from_the_warmup(bench, monkeypatch):
     monkeypatch.setenv("SVO_WATCHDOG_MIN_S", "10")
     monkeypatch.setenv("SVO_WATCHDOG_FACTOR", "1")
     assert bench.watchdog_bound(2.0, 1, 3) == 10.0
+
+
+def test_dump_outputs_keeps_values_and_its_size_bound(bench, tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 files that hold every value unchanged; of an output past the size bound the
+    same seeded sample of rays in every file, identical from run to run"""
+    rng = np.random.default_rng(3)
+    n = 5000
+    hits = {"pos_steps": rng.integers(-20000, 20000, (n, 4)).astype(np.int32), "t": rng.random(n).astype(np.float32),
+            "info": rng.integers(-2**31, 2**31 - 1, n).astype(np.int32), "ao": rng.integers(0, 21, n).astype(np.uint8)}
+    bench.dump_outputs(str(tmp_path / "a"), hits)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(got) == sorted(hits)  # everything fits: no sample, no ray_index
+    assert got["pos_steps"].dtype == np.float32 and got["t"].dtype == np.float32 and got["ao"].dtype == np.float32
+    assert got["info"].dtype == np.float64  # 32-bit words are not float32 values
+    for k in hits:
+        assert got[k].shape == hits[k].shape and np.array_equal(got[k].astype(hits[k].dtype), hits[k]), k
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 40000)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), hits)
+    b = {f[:-4]: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    c = {f[:-4]: np.load(tmp_path / "c" / f) for f in os.listdir(tmp_path / "c")}
+    assert sorted(b) == sorted(list(hits) + ["ray_index"])
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 40000
+    idx = b["ray_index"].astype(np.int64)
+    assert 0 < len(idx) < n and np.all(np.diff(idx) > 0)
+    for k in hits:
+        assert np.array_equal(b[k].astype(hits[k].dtype), hits[k][idx]), k
+        assert np.array_equal(b[k], c[k])
+    assert np.array_equal(b["ray_index"], c["ray_index"])

@@ -17,7 +17,7 @@ rc=$?; echo "pytest rc=$rc" | tee -a "$OUT/steps.log"; tail -5 "$OUT/pytest_gpu.
 if fatal $rc; then exit $rc; fi
 
 echo "[gpu_round] $(date) bench" | tee -a "$OUT/steps.log"
-timeout -k 10 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc=$?; echo "bench rc=$rc" | tee -a "$OUT/steps.log"; cat "$OUT/bench.json"; tail -3 "$OUT/bench.err"
 if [ $rc -ne 0 ]; then exit $rc; fi
 

@@ -1,5 +1,5 @@
 // svo_common.h — definitions shared by the host builder (svo_world.cpp) and the gfx950 kernels
-// (svo_cast.hip).  Everything arithmetic here is compiled with -ffp-contract=off on both sides and
+// (svo_cast_kernel.h).  Everything arithmetic here is compiled with -ffp-contract=off on both sides and
 // rounds identically on x86-64 and gfx950: float divisions and square roots go through double
 // precision and are rounded once to float (double rounding is innocuous for +,-,*,/,sqrt when the
 // wide format has >= 2p+2 bits: 53 >= 50), so no result depends on a compiler's fp32 div/sqrt mode.

@@ -1,4 +1,4 @@
-// svo_hip.h — error plumbing shared by the HIP translation units (svo_cast.hip, svo_build.hip)
+// svo_hip.h — error plumbing shared by the HIP translation units (svo_cast.hip, svo_device.hip, svo_hits_wire.hip, svo_build.hip)
 #pragma once
 
 #include <hip/hip_runtime.h>

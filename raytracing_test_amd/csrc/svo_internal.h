@@ -1,5 +1,5 @@
-// svo_internal.h — host-side object layouts shared by svo_world.cpp (builders, C++ host) and
-// svo_cast.hip (device upload + kernels).  Not part of the public ABI (include/svo_rt.h).
+// svo_internal.h — host-side object layouts shared by svo_world.cpp and svo_plan.cpp (builders and launch
+// planning, C++ host) and the HIP translation units (device residency, launches).  Not part of the public ABI (include/svo_rt.h).
 #pragma once
 
 #include <stdint.h>
@@ -49,18 +49,18 @@ struct svo_tree {
     std::vector<svo::Material> palette;   // id 0 = empty block {0, ~0, 0}
     uint64_t nodes_per_level[8] = {0};
     uint64_t n_bricks = 0;
-    // device side (svo_cast.hip)
+    // device side (svo_device.hip)
     int32_t device = -1;
     void* d_nodes = nullptr;
     void* d_mats = nullptr;
     void* d_pick = nullptr;   // device side buffer (kSideBytes): the pick ray's record, the guard-trip counter (offsets below)
     void* d_pal = nullptr;    // palette for shading: u64 colour[n] then u32 flags[n]
-    // hemisphere AO plan (svo_cast.hip, built on first use for (ao_samples, ao_steps))
+    // hemisphere AO plan (svo_plan.cpp ao_plan_image; svo_cast.hip uploads it, built on first use for (ao_samples, ao_steps))
     mutable void* d_ao_plan = nullptr;
     mutable int32_t ao_plan_n = 0, ao_plan_steps = -1;
     mutable std::mutex pick_mu;  // one pick ray at a time per tree (d_pick)
     uint64_t device_bytes = 0;
-    // incremental edits (svo_tree_update in svo_world.cpp, svo_tree_sync in svo_cast.hip): changed
+    // incremental edits (svo_tree_update in svo_world.cpp, svo_tree_sync in svo_device.hip): changed
     // node blocks are appended; superseded ones are garbage until the next full rebuild
     uint64_t garbage_nodes = 0, garbage_mats = 0;
     uint64_t synced_nodes = 0, synced_mats = 0;  // prefix of nodes / mats already in HBM
@@ -131,8 +131,8 @@ void ceilings_coarsen(const svo_tree* t, std::vector<int16_t>& out, const int64_
 // every level over the columns [x0, x1) x [z0, z1) recomputed from the tree (an edit's region: svo_tree_sync)
 void ceilings_update_rect(const svo_tree* t, std::vector<int16_t>& out, const int64_t off[kCeilMax], int32_t nlev, int64_t x0, int64_t z0,
                           int64_t x1, int64_t z1);
-void tree_release_device(svo_tree* t);  // svo_cast.hip
+void tree_release_device(svo_tree* t);  // svo_device.hip
 // take over device arrays built on `device` (node_cap / mat_cap elements allocated, the host image
-// already equal to their first nodes.size() / mats.size() elements): svo_cast.hip
+// already equal to their first nodes.size() / mats.size() elements): svo_device.hip
 int adopt_device(svo_tree* t, int32_t device, void* d_nodes, uint64_t node_cap, void* d_mats, uint64_t mat_cap);
 }

@@ -1,0 +1,253 @@
+// svo_plan.cpp — the host arithmetic of svo_plan.h: the AO plan's simulation, a frame launch's octant, segment and
+// axis set-up, the ceiling pair / quad tables, what a sync has to move, and the frame schedule's decisions.
+#include "svo_plan.h"
+
+#include <math.h>
+
+#include <algorithm>
+
+namespace svo {
+
+// The AO plan of (n samples, `steps`) (see ao_count_plan): every (sample, face) ray simulated with
+// the kernel's DDA from the centre of cell 0 — dda_axis, then dda_step's axis rule in double.
+// Offsets are listed by step index, then sample, first appearance only.
+std::vector<uint32_t> ao_plan_image(int32_t n, int32_t steps, const float* tab) {
+    if (steps > 127 || n > 64) return {};  // offsets are packed in bytes, masks in 64 bits: rays
+    std::vector<std::vector<std::pair<uint32_t, uint64_t>>> faces(6);
+    for (int face = 0; face < 6; face++) {
+        const uint32_t ax = (uint32_t)face >> 1;
+        const int32_t sg = (face & 1) ? -1 : 1;
+        std::vector<std::vector<uint32_t>> seq(n);
+        for (int32_t i = 0; i < n; i++) {
+            float dir[3];
+            ao_dir(tab + 3 * i, ax, sg, dir);
+            double T[3], A[3];
+            int32_t st[3], pos[3] = {0, 0, 0};
+            for (int k = 0; k < 3; k++) {
+                const Dda1 a = dda_axis(0.5f, dir[k]);
+                T[k] = a.dpos;
+                A[k] = (double)(float)a.adelta;
+                st[k] = a.step;
+            }
+            for (int32_t j = 0; j < steps; j++) {
+                const bool cx = (T[0] < T[1]) && (T[0] < T[2]);
+                const bool cy = !cx && (T[1] < T[2]);
+                const int k = cx ? 0 : (cy ? 1 : 2);
+                pos[k] += st[k];
+                T[k] = T[k] + A[k];
+                seq[i].push_back((uint32_t)(pos[0] + 128) | ((uint32_t)(pos[1] + 128) << 8) | ((uint32_t)(pos[2] + 128) << 16));
+            }
+        }
+        auto& f = faces[face];
+        for (int32_t j = 0; j < steps; j++)
+            for (int32_t i = 0; i < n; i++) {
+                const uint32_t key = seq[i][j];
+                size_t e = 0;
+                while (e < f.size() && f[e].first != key) e++;
+                if (e == f.size()) f.push_back({key, 0ull});
+                f[e].second |= 1ull << i;
+            }
+    }
+    struct Brick {
+        uint32_t key;
+        uint64_t vm, um, sm[64];
+    };
+    std::vector<uint32_t> img(2 * 6 * 64, 0u);
+    for (int face = 0; face < 6; face++)
+        for (int al = 0; al < 64; al++) {
+            const int32_t a[3] = {al & 3, (al >> 2) & 3, al >> 4};
+            std::vector<Brick> bricks;  // in order of first use
+            for (const auto& f : faces[face]) {
+                uint32_t key = 0u, v = 0u;
+                for (int k = 0; k < 3; k++) {
+                    const int32_t p = a[k] + (int32_t)((f.first >> (8 * k)) & 255u) - 128;  // from lastPos's brick corner
+                    key |= (uint32_t)((p >> 2) + 128) << (8 * k);                            // floor division
+                    v |= (uint32_t)(p & 3) << (2 * k);
+                }
+                size_t b = 0;
+                while (b < bricks.size() && bricks[b].key != key) b++;
+                if (b == bricks.size()) {
+                    bricks.push_back(Brick{});
+                    bricks.back().key = key;
+                }
+                bricks[b].vm |= 1ull << v;
+                bricks[b].um |= f.second;
+                bricks[b].sm[v] |= f.second;
+            }
+            const size_t g = (size_t)face * 64 + (size_t)al;
+            img[2 * g] = (uint32_t)(img.size() / 4);
+            img[2 * g + 1] = (uint32_t)bricks.size();
+            for (const Brick& b : bricks) {
+                const uint32_t rec[8] = {b.key, 0u, (uint32_t)b.vm, (uint32_t)(b.vm >> 32), (uint32_t)b.um, (uint32_t)(b.um >> 32), 0u, 0u};
+                img.insert(img.end(), rec, rec + 8);
+                for (int v = 0; v < 64; v++)
+                    if ((b.vm >> v) & 1ull) {
+                        img.push_back((uint32_t)b.sm[v]);
+                        img.push_back((uint32_t)(b.sm[v] >> 32));
+                    }
+                while (img.size() % 4) img.push_back(0u);
+            }
+        }
+    return img;
+}
+
+// The launch's step-sign octant (1..8, dirs_sign) when every frame ray has the same step signs, else 0.
+// A pixel's direction before normalisation (raygen_pixel) is an affine function of the pixel, so its
+// extremes are at the frame's corners; a corner value beyond 1e-4 of the terms' magnitudes keeps
+// every pixel's rounded value (errors of a few ulps of those terms) on the same side of zero, and
+// normalisation keeps the sign.  (Explicit rays have none: 0 without a call.)
+int frame_dirs(const RayGen& rg, int32_t width, int32_t height, int32_t flags) {
+    if (flags & SVO_CAST_NO_OCTANT) return 0;
+    int code = 1;
+    for (int a = 0; a < 3; a++) {
+        int pos = 0, neg = 0;
+        for (int c = 0; c < 4; c++) {
+            const int32_t px = (c & 1) ? width - 1 : 0, py = (c & 2) ? height - 1 : 0;
+            const float fx = ((float)px + 0.5f) * rg.rw, fy = ((float)py + 0.5f) * rg.rh;
+            const float sl = -(rg.ppx * (fx - 0.5f)), su = -fy + 0.5f;
+            const float lt = rg.l[a] * sl, ut = (rg.u[a] * su) * rg.ppy;
+            const float v = (rg.c[a] + lt) + ut;
+            const float mag = fabsf(rg.c[a]) + fabsf(rg.l[a]) * fabsf(rg.ppx) + fabsf(rg.u[a] * rg.ppy);
+            if (v > 1e-4f * mag) pos++;
+            else if (v < -1e-4f * mag) neg++;
+        }
+        if (pos == 4) continue;
+        if (neg == 4) code += 1 << a;
+        else return 0;
+    }
+    return code;
+}
+
+// Can the launch hold rays that are not linear (svo_trace.h, "Exact closed-form skipping")?  From an
+// integral or half-integral origin every ray is (lin_origin, with budgets below 2^28 every sum it
+// takes is exact); explicit rays are not inspected.  The instance without segments relies on it
+// (trace: TRACK); SVO_CAST_SEGMENTS forces the other one (the same results).
+// org: the launch's n_org origins (a frame launch's frame origins, else the one origin).
+bool need_seg(int32_t flags, bool explicit_rays, int32_t steps, const float* org, int32_t n_org) {
+    if (flags & SVO_CAST_SEGMENTS) return true;
+    if (explicit_rays || steps >= (1 << 28)) return true;
+    for (int32_t i = 0; i < 3 * n_org; i++)
+        if (!(2.0f * org[i] == __builtin_truncf(2.0f * org[i]) && __builtin_fabsf(org[i]) < 1073741824.0f)) return true;
+    return false;
+}
+
+// the octant's frame set-up (FrameAxes, svo_cast_params.h) for a frame cast from org
+void frame_axes(int dirs, const float org[3], double frac[3], int32_t cell[3]) {
+    for (int k = 0; k < 3; k++) {
+        const float o = org[k];
+        cell[k] = (int32_t)__builtin_truncf(o);
+        const double exact = ((dirs - 1) >> k) & 1 ? (double)o - 1.0 : (double)o;
+        frac[k] = exact - (double)cell[k];
+    }
+}
+
+// The ceiling pairs of level j (its block's ceiling, low 16 bits; its level-(j + kCeilPairStep) block's, high, or the coarsest
+// level's when the tree has fewer) over the blocks holding columns [x0, x1) x [z0, z1) — widened to whole parent blocks, whose change reaches
+// every child's pair.  Returns per level the first and last row written (level j's rows of blocks, row-major [z][x]).
+static void ceil_pairs(svo_tree* t, int32_t n, int64_t x0, int64_t z0, int64_t x1, int64_t z1, int64_t zr[kCeilMax][2]) {
+    for (int32_t j = 0; j < n; j++) {
+        const int64_t rows = (int64_t)1 << (2 * (t->levels - kCeilK0 - j));
+        const int32_t up = std::min(j + kCeilPairStep, n - 1), sh = 2 * (up - j);
+        const int32_t ush = 2 * (kCeilK0 + up), bsh = 2 * (kCeilK0 + j);
+        const int64_t rows_up = rows >> sh;
+        const int64_t bz0 = (z0 >> ush) << (ush - bsh), bz1 = std::min(rows, (((z1 - 1) >> ush) + 1) << (ush - bsh));
+        const int64_t bx0 = (x0 >> ush) << (ush - bsh), bx1 = std::min(rows, (((x1 - 1) >> ush) + 1) << (ush - bsh));
+        const int16_t* c = t->ceil_host.data();
+        for (int64_t z = bz0; z < bz1; z++)
+            for (int64_t x = bx0; x < bx1; x++)
+                t->ceilp_host[t->ceil_off[j] + z * rows + x] = (uint32_t)(uint16_t)c[t->ceil_off[j] + z * rows + x] |
+                                                                 ((uint32_t)(uint16_t)c[t->ceil_off[up] + (z >> sh) * rows_up + (x >> sh)] << 16);
+        zr[j][0] = bz0;
+        zr[j][1] = bz1;
+    }
+}
+
+// The ceiling quads (svo_tree.d_ceilq) of the level-0 blocks holding columns [x0, x1) x [z0, z1), widened to whole blocks of
+// the coarsest level (whose change reaches every level-0 block inside it).  Returns the first and last row written.
+static void ceil_quads(svo_tree* t, int32_t n, int64_t x0, int64_t z0, int64_t x1, int64_t z1, int64_t zr[2]) {
+    const int64_t rows = (int64_t)1 << (2 * (t->levels - kCeilK0));
+    const int32_t tsh = 2 * (n - 1);  // the coarsest level's blocks, in level-0 blocks (log2)
+    const int32_t bsh = 2 * kCeilK0 + tsh;
+    const int64_t bz0 = (z0 >> bsh) << tsh, bz1 = std::min(rows, (((z1 - 1) >> bsh) + 1) << tsh);
+    const int64_t bx0 = (x0 >> bsh) << tsh, bx1 = std::min(rows, (((x1 - 1) >> bsh) + 1) << tsh);
+    const int16_t* c = t->ceil_host.data();
+    for (int64_t z = bz0; z < bz1; z++)
+        for (int64_t x = bx0; x < bx1; x++) {
+            uint64_t q = 0;
+            for (int32_t j = 0; j < kCeilMax; j++) {
+                const int16_t v = j < n ? c[t->ceil_off[j] + (z >> (2 * j)) * (rows >> (2 * j)) + (x >> (2 * j))] : (int16_t)0x7FFF;
+                q |= (uint64_t)(uint16_t)v << (16 * j);
+            }
+            t->ceilq_host[z * rows + x] = q;
+        }
+    zr[0] = bz0;
+    zr[1] = bz1;
+}
+
+int32_t ceil_tables_build(svo_tree* t) {
+    int64_t off[kCeilMax] = {0, 0, 0, 0}, zr[kCeilMax][2], qr[2];
+    const int32_t n = tree_ceilings(t, t->ceil_host, off);
+    for (int j = 0; j < kCeilMax; j++) t->ceil_off[j] = t->ceilp_off[j] = off[j];
+    t->ceilp_host.assign(t->ceil_host.size(), 0u);
+    t->ceilq_host.clear();
+    if (n > 0) {
+        const int64_t e = (int64_t)1 << (2 * t->levels);
+        ceil_pairs(t, n, 0, 0, e, e, zr);
+        t->ceilq_host.assign((size_t)1 << (4 * (t->levels - kCeilK0)), 0ull);
+        ceil_quads(t, n, 0, 0, e, e, qr);
+    }
+    return n;
+}
+
+void ceil_tables_update(svo_tree* t, int32_t n, const std::array<int64_t, 4>& r, int64_t zr[kCeilMax][2], int64_t qr[2]) {
+    ceilings_update_rect(t, t->ceil_host, t->ceil_off, n, r[0], r[1], r[2], r[3]);
+    ceil_pairs(t, n, r[0], r[1], r[2], r[3], zr);
+    ceil_quads(t, n, r[0], r[1], r[2], r[3], qr);
+}
+
+std::vector<std::pair<uint32_t, uint32_t>> dirty_runs(std::vector<uint32_t>& dirty) {
+    std::vector<std::pair<uint32_t, uint32_t>> runs;
+    std::sort(dirty.begin(), dirty.end());
+    for (size_t i = 0; i < dirty.size();) {
+        size_t j = i + 1;
+        while (j < dirty.size() && dirty[j] <= dirty[j - 1] + 1) j++;
+        runs.push_back({dirty[i], dirty[j - 1]});
+        i = j;
+    }
+    return runs;
+}
+
+bool tree_unsynced(const svo_tree* t) {
+    return t->full_upload || t->nodes.size() != t->synced_nodes || t->mats.size() != t->synced_mats || !t->dirty_nodes.empty() ||
+           t->palette_dirty || !t->ceil_dirty.empty();
+}
+
+SchedPlan sched_decide(svo_tree::Sched& s, int64_t blocks, const int64_t sig[7], const float cam[6]) {
+    if (s.blocks != blocks || !std::equal(sig, sig + 7, s.sig)) {
+        s.blocks = blocks;
+        std::copy(sig, sig + 7, s.sig);
+        s.primed = false;
+    }
+    const auto close = [&](const float* c) {
+        const float dx = cam[0] - c[0], dy = cam[1] - c[1], dz = cam[2] - c[2];
+        return dx * dx + dy * dy + dz * dz <= kSchedMove * kSchedMove && cam[3] * c[3] + cam[4] * c[4] + cam[5] * c[5] >= kSchedTurnCos;
+    };
+    const bool near_last = close(s.last_cam);          // (a frame far from the last one is not sorted after)
+    const bool near_sorted = s.primed && close(s.cam);  // (the order is used only near the frame it was sorted from)
+    std::copy(cam, cam + 6, s.last_cam);
+    if (!near_last) {  // (a moving camera: no sort after this frame; the first frame near it sorts for the next)
+        s.primed = false;
+        return SchedPlan{near_sorted, false, false};
+    }
+    // sorted after this frame: an order missing or sorted from a camera this one has drifted from, else every
+    // kSchedEvery-th frame.  Only the frames sorted after write their durations, so the stored order is always the sort of
+    // the stored durations (svo_tree_schedule)
+    const bool sort = !near_sorted || ++s.since >= kSchedEvery;
+    if (sort) {
+        s.since = 0;
+        std::copy(cam, cam + 6, s.cam);
+    }
+    return SchedPlan{near_sorted, sort, sort};
+}
+
+}  // namespace svo

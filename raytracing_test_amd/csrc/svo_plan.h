@@ -1,0 +1,48 @@
+// svo_plan.h — the host arithmetic behind a launch and behind device residency: no HIP, so it also builds with g++
+// and runs on a CPU (tests/sanitize/host_sanitize.cpp).  The HIP translation units act on its results.
+#pragma once
+
+#include <utility>
+
+#include "svo_internal.h"
+
+namespace svo {
+
+// The AO plan of (n samples, `steps`) as the image ao_count_plan reads (svo_shade.h); empty: no plan for them
+std::vector<uint32_t> ao_plan_image(int32_t n, int32_t steps, const float* tab);
+
+int frame_dirs(const RayGen& rg, int32_t width, int32_t height, int32_t flags);
+bool need_seg(int32_t flags, bool explicit_rays, int32_t steps, const float* org, int32_t n_org);
+void frame_axes(int dirs, const float org[3], double frac[3], int32_t cell[3]);
+
+// The host copies of the ceiling tables (svo_tree.ceil_host / ceilp_host / ceilq_host, ceil_off): rebuilt whole from the
+// tree (returns the number of levels), or brought up to date over one rectangle of svo_tree.ceil_dirty, which returns the
+// rows rewritten, first and one past the last: zr per level of the ceilings and pairs, qr of the quads.  Both may throw
+// std::bad_alloc.
+int32_t ceil_tables_build(svo_tree* t);
+void ceil_tables_update(svo_tree* t, int32_t n, const std::array<int64_t, 4>& r, int64_t zr[kCeilMax][2], int64_t qr[2]);
+
+// the tree's rewritten records (svo_tree.dirty_nodes, sorted here) as runs [first, last] of consecutive indices
+std::vector<std::pair<uint32_t, uint32_t>> dirty_runs(std::vector<uint32_t>& dirty);
+// the host image holds something its copy in HBM does not (svo_tree_sync would move data)
+bool tree_unsynced(const svo_tree* t);
+
+// A schedule predicts a frame from the last one: a camera that turned more than kSchedTurn or moved more than kSchedMove
+// voxels since runs the default order (and re-primes).  Measured (tools/shade_motion.py, r04_ax): a still view 0.462 ->
+// 0.368 ms; 0.25 deg + 0.14 voxels per frame 0.400 -> 0.395; 2 deg per frame 0.292 -> 0.374 and a cut every frame
+// 0.308 -> 0.358 when a stale order was used — a wrong order is worse than the default one.  A frame far from the last
+// one is not sorted after either (the sort costs ~9 us): the schedule comes back one frame after the camera settles.
+constexpr float kSchedTurnCos = 0.99996f;  // cos(0.5 deg)
+// A still camera's order holds for the next frames too: a scheduled frame writes its durations and is sorted after only
+// every kSchedEvery-th frame (the sort, one workgroup for ~9 us between two launches, is otherwise on every frame's path)
+constexpr int32_t kSchedEvery = 4;
+constexpr float kSchedMove = 1.0f;
+struct SchedPlan {
+    bool use_order;   // dispatch in the stored order
+    bool write_cost;  // the blocks write their durations
+    bool sort;        // the durations are sorted into the next order after the launch (sched_order, which primes)
+};
+// this frame's use of schedule s (its buffer already holds `blocks` blocks), and s moved on to it
+SchedPlan sched_decide(svo_tree::Sched& s, int64_t blocks, const int64_t sig[7], const float cam[6]);
+
+}  // namespace svo

@@ -1,6 +1,6 @@
 // svo_wire.h — the wire formats of hit records (include/svo_rt.h) for the tile-row gather: encoding (the
 // cast kernel's fused output, svo_hits_pack) and decoding (svo_hits_unpack, svo_wire_scatter, the
-// exchange's receive side), shared by svo_cast.hip and svo_exchange.hip.
+// exchange's receive side), shared by svo_cast_kernel.h, svo_hits_wire.hip and svo_exchange.hip.
 //
 //   12 B (any desc):  int16 dx, dy, dz = pos - trunc(origin) | u16 hit << 15 | axis << 13 | (step < 0) << 12 |
 //                     material (12 bits) | f32 t
@@ -12,7 +12,7 @@
 // record's pixel, so it regenerates the ray (raygen_pixel, dda_axis, the same code the kernel runs) and
 // recovers the step signs, the position (cell + s n), the steps left (a hit: steps - n_x - n_y - n_z) and
 // t.  From such origins deltaPos starts at a, 0, a/2, 3a/2 or -a/2 and every crossing sum the DDA takes is
-// exact (svo_cast.hip, lin_origin), so after n steps on the last axis its deltaPos is fma(n, a, T0) —
+// exact (svo_trace.h, lin_origin), so after n steps on the last axis its deltaPos is fma(n, a, T0) —
 // the double the kernel holds — and t = that - a (an infinite absDelta keeps it as is: inf or NaN, as
 // the kernel's recovery does).
 #pragma once

@@ -1,7 +1,7 @@
 """Trees whose root is not an ordinary interior node, and near-empty worlds.  Every trace seeds its first parent from
 the root (round 6: node 0 read once, uniform); a root that is not interior — a uniform world (the root itself a SOLID
 block, putBlock at level 1), a one-level 4^3 tree (the root is the only brick) — keeps the virtual parent above it
-(svo_cast.hip trace()).  Frames on such trees, on an empty world and on a world of one far block, against the oracle's
+(svo_trace.h trace()).  Frames on such trees, on an empty world and on a world of one far block, against the oracle's
 castRayFromCam (ray_caster.cpp:54-87 over tetrahexa_tree.cpp:113-157), every field bit-exact, with and without
 ceilings and with voxel stepping (tests/test_gpu_parity.py compare)."""
 import numpy as np

@@ -110,7 +110,7 @@ def test_patched_tree_casts_match_oracle(rt, oracle_mod, torch_cuda):
 
 
 def _pairs_of(c, E, k0, lv, step):
-    """the pair table the kernels read, derived from the ceilings (svo_cast.hip ceil_pairs): level j with level
+    """the pair table the kernels read, derived from the ceilings (svo_plan.cpp ceil_pairs): level j with level
     min(j + step, lv - 1)"""
     offs, o = [], 0
     for j in range(lv):

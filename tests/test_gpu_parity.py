@@ -439,7 +439,7 @@ def test_depth12_half_integral_camera(rt, depth12, oracle12, org):
                                         (((4, 90, 4), (1, 0.3, 1)), 3000), (((2000.5, 70.25, 1000.75), (-0.3, 0.2, 1)), 777)])
 def test_depth12_budget_ends_in_air(rt, depth12, oracle12, pose, steps):
     """Budgets that end in empty space, far from any voxel: those lanes leave the traversal loop
-    and take their last DDA steps after it (svo_cast.hip, trace); sampled pixels against the oracle,
+    and take their last DDA steps after it (svo_trace.h, trace); sampled pixels against the oracle,
     every output field, also for a fractional origin (rays that are not exact walk empty bricks)."""
     org, d = pose
     T = oracle12
@@ -459,7 +459,7 @@ def test_depth12_budget_ends_in_air(rt, depth12, oracle12, pose, steps):
 @pytest.mark.parametrize("org", [(4.37, 90.61, 4.23), (-7.3, 88.125, 1000.01)])
 def test_depth12_fractional_camera(rt, depth12, oracle12, org):
     """C3 from non-integral camera positions, S = 16384: the rays are not linear (their crossings
-    round once per binade), so the kernel crosses empty regions in exact segments (svo_cast.hip,
+    round once per binade), so the kernel crosses empty regions in exact segments (svo_trace.h,
     seg_cap).  Sampled pixels (top and bottom rows, the horizon band) against the oracle; the whole
     frame identical to the voxel-by-voxel path; still O(1) crossings (not voxel stepping)."""
     T = oracle12
@@ -513,7 +513,7 @@ def test_depth12_full_frame_properties(rt, depth12):
 @pytest.mark.parametrize("octant", range(8))
 def test_octant_frames(rt, gtree, ref_world_oracle, octant):
     """Frames whose rays all step with one sign octant run an instance with the signs compiled in
-    (svo_cast.hip: frame_dirs); every octant, integral and fractional origins, against the oracle and
+    (svo_plan.cpp: frame_dirs); every octant, integral and fractional origins, against the oracle and
     against the per-wave sign flags (SVO_CAST_NO_OCTANT)."""
     sx, sy, sz = [(-1.0 if (octant >> k) & 1 else 1.0) for k in range(3)]
     dn = rt.normalize([sx * 1.0, sy * 0.45, sz * 0.8])

@@ -1,6 +1,6 @@
 """Host code under AddressSanitizer + UndefinedBehaviorSanitizer (+ LeakSanitizer), SURVEY.md §5: the
 product's host half (raytracing_test_amd/csrc/svo_world.cpp: edits, every builder in both views, patching,
-lookups, checkpoint) and the oracle (oracle/oracle.c: casts, AO, shading, deleteBlock), each driven by a
+lookups, checkpoint; svo_plan.cpp: the launch planning, the ceiling tables, the AO plan, the schedule's decisions) and the oracle (oracle/oracle.c: casts, AO, shading, deleteBlock), each driven by a
 small program in tests/sanitize/ and built with gcc here.  GPU sanitizers are not available on the pool;
 these run on the CPU only."""
 import os
@@ -23,7 +23,8 @@ def _run(cmd, **kw):
 def test_host_library_clean_under_asan_ubsan(tmp_path):
     exe = str(tmp_path / "host_sanitize")
     _run(["g++", "-std=c++17"] + SAN + ["-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "sanitize", "host_sanitize.cpp"),
-                                       os.path.join(ROOT, "raytracing_test_amd", "csrc", "svo_world.cpp"), "-o", exe])
+                                       os.path.join(ROOT, "raytracing_test_amd", "csrc", "svo_world.cpp"),
+                                       os.path.join(ROOT, "raytracing_test_amd", "csrc", "svo_plan.cpp"), "-o", exe])
     out = _run([exe, str(tmp_path / "t.svo")], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     assert "host sanitize ok" in out
 

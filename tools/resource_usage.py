@@ -1,13 +1,19 @@
-"""Per-kernel register / spill / occupancy table of a HIP source (hipcc -Rpass-analysis=kernel-resource-usage).
-usage: python tools/resource_usage.py [source.hip] [extra hipcc flags...]"""
+"""Per-kernel register / spill / occupancy table of HIP sources (hipcc -Rpass-analysis=kernel-resource-usage).
+usage: python tools/resource_usage.py [source.hip] [extra hipcc flags...]   (default: every source of the library)"""
+import os
 import re
 import subprocess
 import sys
 
-src = sys.argv[1] if len(sys.argv) > 1 else "raytracing_test_amd/csrc/svo_cast.hip"
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-c", src,
-       "-o", "/tmp/_ru.o", "-Rpass-analysis=kernel-resource-usage"] + sys.argv[2:]
-err = subprocess.run(cmd, capture_output=True, text=True).stderr
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "raytracing_test_amd"))
+import build  # noqa: E402
+
+srcs = [sys.argv[1]] if len(sys.argv) > 1 else [os.path.join(build.CSRC, s) for s in build.HIP_SRCS]
+err = ""
+for src in srcs:
+    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-c", src,
+           "-o", "/tmp/_ru.o", "-Rpass-analysis=kernel-resource-usage"] + sys.argv[2:]
+    err += subprocess.run(cmd, capture_output=True, text=True).stderr
 cur, rows = None, []
 for line in err.splitlines():
     m = re.search(r"remark:\s+([A-Za-z /\[\]]+?): (.*?) \[-Rpass", line)

@@ -27,7 +27,9 @@ extern "C" {
                              4: tree views (liquid stored for the shading pass), svo_shade_desc.scene / time;
                              6: svo_tree_save / svo_tree_load (5, a cost-ordered dispatch, was measured slower
                              and removed); 7: 8-B compact wire records, svo_wire_bytes / svo_cast_wire /
-                             svo_wire_scatter / svo_exchange_wire */
+                             svo_wire_scatter / svo_exchange_wire.  Entry points added since keep the number and are
+                             detected by symbol (dlsym / hasattr): svo_build_volume_gpu, svo_tree_read_volume,
+                             svo_volume_classify_pass */
 
 enum {
     SVO_OK = 0,
@@ -135,6 +137,42 @@ int svo_build_heightfield(int32_t levels, int32_t width, int32_t length, const i
 int svo_build_terrain_gpu(int32_t levels, int32_t width, int32_t length, int32_t device, svo_tree** out);
 int svo_build_terrain_gpu_view(int32_t levels, int32_t width, int32_t length, int32_t device, int32_t view, svo_tree** out);
 int svo_build_heightfield_gpu(int32_t levels, int32_t width, int32_t length, const int32_t* heights, int32_t device, svo_tree** out);
+/* A tree from a dense voxel volume already in HBM (a torch tensor from a generator, a voxelised model, a simulation
+   grid): arbitrary content — overhangs, caves, floating blocks, any palette — without a host world.  A class pyramid
+   over the volume's world-aligned bounding box (level 1 reads the volume once: one class per 4^3 brick; each level
+   above folds 64 children) feeds the level-synchronous emitter of the terrain builders.  The output is the canonical
+   linearisation: nodes, material runs, nodes_per_level, n_bricks and palette equal, byte for byte, what svo_build_view
+   emits for a world holding the same blocks under the same palette ids.
+     palette   entries other than 0 are stored with flags 1 | flags, as putBlock stores them
+     view      an id is stored when the view holds its palette entry: LIQUID ids and ids whose colour is ~0 are empty
+               in SVO_VIEW_SOLID, only ids whose colour is ~0 in SVO_VIEW_ALL
+   SVO_EINVAL: NULL pointers, levels outside 2..7, a non-positive dimension, a box that leaves the extent, an unknown
+   view, palette[0] not the empty block; SVO_ERANGE: n_palette outside 1..65535, a voxel id >= n_palette (found on
+   the device by the first pass; nothing is emitted); SVO_ENOMEM: no scratch.  Arguments are checked before the first
+   HIP call.  The device is synchronised on entry (the volume may come from any stream); the build runs on the null
+   stream.  Such a tree has no svo_world behind it: svo_tree_update stays a world-only path, a volume tree is rebuilt
+   from a new volume, not patched. */
+typedef struct {
+    int32_t levels;              /* extent 4^levels per axis; 2..7 like the other GPU builders */
+    int32_t nx, ny, nz;          /* voxels; voxels[((int64)z * ny + y) * nx + x] — a contiguous (nz, ny, nx) tensor */
+    int32_t origin[3];           /* world position of voxels[0]; any integers with origin + n <= extent, >= 0 (no wrap) */
+    const uint16_t* voxels;      /* DEVICE pointer on `device`: palette ids, 0 = empty */
+    const svo_block* palette;    /* HOST: n_palette entries; entry 0 must be the empty block {0, ~0ull, 0} */
+    uint32_t n_palette;          /* 1..65535 */
+    int32_t view;                /* SVO_VIEW_SOLID / SVO_VIEW_ALL */
+    int32_t device;
+} svo_volume_desc;
+/* the canonical tree of that content, built in HBM, returned uploaded to `device` with its host image
+   (like svo_build_terrain_gpu); voxels outside the box are empty */
+int svo_build_volume_gpu(const svo_volume_desc* v, svo_tree** out);
+/* the palette id the tree stores (its view) for every voxel of the box origin .. origin + n, written to a
+   device buffer in the same (nz, ny, nx) layout; coordinates wrap modulo the extent as svo_tree_get_blocks'
+   do; asynchronous on hip_stream; tree must be uploaded (SVO_ESTATE otherwise) */
+int svo_tree_read_volume(const svo_tree* t, const int32_t origin[3], int32_t nx, int32_t ny, int32_t nz,
+                         uint16_t* voxels, void* hip_stream);
+/* diagnostics (tools/volume_build_timing.py): svo_build_volume_gpu's first pass alone — the level-1 classification,
+   which reads the whole volume — run `runs` times into scratch, each timed by HIP events: ms[0 .. runs-1] */
+int svo_volume_classify_pass(const svo_volume_desc* v, int32_t runs, float* ms);
 int svo_tree_get_info(const svo_tree* t, svo_tree_info* out);
 /* palette entry `id` (id 0 = empty block) */
 int svo_tree_palette(const svo_tree* t, uint32_t id, svo_block* out);

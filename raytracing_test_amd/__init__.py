@@ -117,6 +117,14 @@ class CastDesc(C.Structure):
     ]
 
 
+class VolumeDesc(C.Structure):
+    """svo_volume_desc: a dense (nz, ny, nx) volume of palette ids in HBM, placed at `origin` of a 4^levels world"""
+
+    _fields_ = [("levels", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("origin", C.c_int32 * 3),
+                ("voxels", C.c_void_p), ("palette", C.POINTER(Block)), ("n_palette", C.c_uint32), ("view", C.c_int32),
+                ("device", C.c_int32)]
+
+
 class Hits(C.Structure):
     _fields_ = [("pos_steps", C.c_void_p), ("t", C.c_void_p), ("info", C.c_void_p), ("ao", C.c_void_p)]
 
@@ -146,7 +154,7 @@ ABI_SYMBOLS = (
     "svo_exchange_frames", "svo_build_view", "svo_build_terrain_view", "svo_build_terrain_gpu_view",
     "svo_tree_save", "svo_tree_load", "svo_wire_bytes", "svo_cast_wire", "svo_wire_scatter", "svo_exchange_wire", "svo_tree_ceilings",
     "svo_tree_guard_trips", "svo_ceiling_layout", "svo_tree_device_ceilings", "svo_tree_device_ceiling_quads", "svo_tree_schedule", "svo_cast_ray_from_cam_async",
-    "svo_build_id",
+    "svo_build_id", "svo_build_volume_gpu", "svo_tree_read_volume", "svo_volume_classify_pass",
 )
 
 
@@ -224,7 +232,10 @@ def lib():
                      ("svo_tree_device_ceilings", [vp, vp, vp, C.c_int64, C.POINTER(i32), C.POINTER(C.c_int64)]),
                      ("svo_tree_device_ceiling_quads", [vp, vp, C.c_int64, C.POINTER(C.c_int64)]),
                      ("svo_tree_schedule", [vp, vp, C.c_int32, vp, vp, C.c_int64, C.POINTER(C.c_int64)]),
-                     ("svo_cast_ray_from_cam_async", [vp, f3, f3, i32, vp, vp])):
+                     ("svo_cast_ray_from_cam_async", [vp, f3, f3, i32, vp, vp]),
+                     ("svo_build_volume_gpu", [C.POINTER(VolumeDesc), C.POINTER(vp)]),
+                     ("svo_tree_read_volume", [vp, C.POINTER(i32), i32, i32, i32, vp, vp]),
+                     ("svo_volume_classify_pass", [C.POINTER(VolumeDesc), i32, C.POINTER(f32)])):
         if hasattr(L, name):
             getattr(L, name).argtypes = at
     L.svo_build_terrain.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
@@ -476,6 +487,72 @@ class Tree:
         _check(lib().svo_build_heightfield_gpu(levels, h.shape[0], h.shape[1], h.ctypes.data_as(C.c_void_p), device, C.byref(t)),
                "svo_build_heightfield_gpu")
         return cls(t)
+
+    @staticmethod
+    def volume_desc(levels, voxels, palette, origin=(0, 0, 0), view=VIEW_SOLID, device=0):
+        """(VolumeDesc, the device tensor it points to) for volume_gpu's arguments, validated: ValueError for a wrong
+        dtype, rank or device or a non-contiguous tensor, before the library is called"""
+        torch = _torch()
+        if isinstance(voxels, np.ndarray):
+            if voxels.dtype != np.uint16 or voxels.ndim != 3:
+                raise ValueError("voxels: a numpy volume must be a uint16 array of shape (nz, ny, nx)")
+            voxels = torch.from_numpy(np.ascontiguousarray(voxels).view(np.int16)).to(torch.device("cuda", device))
+        if not isinstance(voxels, torch.Tensor):
+            raise ValueError("voxels: a torch tensor or a numpy uint16 array")
+        if voxels.dtype not in (torch.uint16, torch.int16):
+            raise ValueError("voxels: dtype must be torch.uint16 or torch.int16, not %s" % voxels.dtype)
+        if voxels.dim() != 3 or min(voxels.shape) < 1:
+            raise ValueError("voxels: shape must be (nz, ny, nx), not %s" % (tuple(voxels.shape),))
+        if not voxels.is_contiguous():
+            raise ValueError("voxels: the tensor must be contiguous")
+        if not voxels.is_cuda or voxels.device.index != device:
+            raise ValueError("voxels: the tensor must live on cuda:%d, not %s" % (device, voxels.device))
+        if len(origin) != 3:
+            raise ValueError("origin: three integers")
+        pal = (Block * max(1, len(palette)))()
+        for i, (f, c, m) in enumerate(palette):
+            pal[i] = Block(int(f), int(c), float(m))
+        d = VolumeDesc()
+        d.levels = levels
+        d.nz, d.ny, d.nx = (int(n) for n in voxels.shape)
+        d.origin[:] = [int(o) for o in origin]
+        d.voxels = voxels.data_ptr()
+        d.palette = pal
+        d._palette = pal  # keep the host array alive with the desc
+        d.n_palette = len(palette)
+        d.view = view
+        d.device = device
+        return d, voxels
+
+    @classmethod
+    def volume_gpu(cls, levels, voxels, palette, origin=(0, 0, 0), view=VIEW_SOLID, device=0):
+        """svo_build_volume_gpu: the canonical tree of a dense volume of palette ids, built in HBM and returned uploaded
+        to `device`.  voxels: a contiguous CUDA tensor (nz, ny, nx) of torch.uint16 / torch.int16 (the bits are the ids;
+        0 = empty), or a numpy uint16 array of that shape (uploaded through torch); palette: [(flags, color, metadata)]
+        as Tree.palette() returns it, entry 0 the empty block; origin: the world position of voxels[0, 0, 0] as
+        (x, y, z).  Voxels outside the box are empty.  A volume tree is rebuilt, not patched (update() needs a World)."""
+        d, keep = cls.volume_desc(levels, voxels, palette, origin, view, device)
+        h = C.c_void_p()
+        _check(lib().svo_build_volume_gpu(C.byref(d), C.byref(h)), "svo_build_volume_gpu")
+        del keep
+        return cls(h)
+
+    def read_volume(self, origin, shape, out=None, stream=None):
+        """svo_tree_read_volume: the palette ids this (uploaded) tree stores in the box of `shape` = (nz, ny, nx) voxels
+        at origin (x, y, z), as an int16 CUDA tensor of that shape (the bits are the ids; coordinates wrap modulo the
+        extent); asynchronous on `stream`"""
+        torch = _torch()
+        nz, ny, nx = (int(n) for n in shape)
+        if out is None:
+            out = torch.empty((nz, ny, nx), dtype=torch.int16, device=torch.device("cuda", self.info().device))
+        elif (tuple(out.shape) != (nz, ny, nx) or out.dtype not in (torch.int16, torch.uint16) or not out.is_cuda
+              or not out.is_contiguous()):
+            raise ValueError("out: a contiguous int16 CUDA tensor of shape (nz, ny, nx)")
+        s = getattr(stream, "cuda_stream", stream)
+        o = (C.c_int32 * 3)(*[int(v) for v in origin])
+        _check(lib().svo_tree_read_volume(self._h, o, nx, ny, nz, C.c_void_p(out.data_ptr()), C.c_void_p(s) if s else None),
+               "svo_tree_read_volume")
+        return out
 
     def save(self, path):
         """checkpoint the linearised tree to a file (svo_tree_save)"""

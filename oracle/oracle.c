@@ -1383,9 +1383,15 @@ EXPORT float orc_sin_f32(float x) { return o_sin_f32(x); }
    getBlock, :312-333): refractive liquid (flags & 7 == 5, the terrain's water 0x15) tints by
    (0.94, 0.97, 1.0) (:214) and, when it is the first refractive block, bends the ray with the
    normal's wobble x += sin((time + exact.x * 0.2 - exact.z * 0.1) * 10) * 0.2, renormalised
-   (:225-229; exact as float). */
+   (:225-229; exact as float).
+   ev (optional) receives what happened on the way, for tests that must know what a battery exercised: whether the ray
+   bent, the refractive blocks passed (tints), whether the bending block was liquid, the bend's face (axis and step
+   sign at the bend) and the reflections before the bend.  It only records: no operation of the walk depends on it. */
+typedef struct {
+    int32_t bent, tints, liq_bend, bend_axis, bend_sign, refl_at_bend;
+} o_events;
 static void o_cast_refl(o_getblock_fn gb, const void* world, const float org[3], const float dir_in[3], int steps, orayres* R,
-                        float dir[3], int* nrefl, float mod[3], int liquid, float time) {
+                        float dir[3], int* nrefl, float mod[3], int liquid, float time, o_events* ev) {
     int st[3];
     double dl[3], ad[3], ex[3], dp[3];
     int r[3], last[3];
@@ -1404,6 +1410,10 @@ static void o_cast_refl(o_getblock_fn gb, const void* world, const float org[3],
     R->axis = -1;
     *nrefl = 0;
     mod[0] = mod[1] = mod[2] = 1.0f;
+    if (ev) {
+        memset(ev, 0, sizeof(*ev));
+        ev->bend_axis = -1;
+    }
     for (int a = 0; a < 3; a++) last[a] = r[a];
     while (steps--) {
         int ax;
@@ -1436,8 +1446,16 @@ static void o_cast_refl(o_getblock_fn gb, const void* world, const float org[3],
                 mod[0] *= liq ? 0.94f : 0.95f;
                 mod[1] *= liq ? 0.97f : 0.95f;
                 mod[2] *= liq ? 1.0f : 0.95f;
+                if (ev) ev->tints++;
                 if (!bent) {
                     bent = 1;
+                    if (ev) {
+                        ev->bent = 1;
+                        ev->liq_bend = liq;
+                        ev->bend_axis = ax;
+                        ev->bend_sign = st[ax];
+                        ev->refl_at_bend = *nrefl;
+                    }
                     for (int a = 0; a < 3; a++)
                         if (a != ax && st[a] < 0) ex[a] += 1;
                     float nrm[3] = {0.0f, 0.0f, 0.0f};
@@ -1501,14 +1519,30 @@ static void o_sky(const float d[3], const float sun[3], float o[3]) {
     o[2] = (1.0f + h3) * modifier + 0.0f;
 }
 
+/* what o_shade's primary ray (o_cast_refl) ended with, for orc_shade_rays */
+typedef struct {
+    orayres R;
+    o_events ev;
+    int nrefl;
+    float dir[3], mod[3];
+} o_shrec;
+
 static void o_shade(o_getblock_fn gb, const void* world, const float org[3], const float d0[3], int steps, const float sun[3],
-                    const int32_t* look, int shadow_steps, int liquid, float time, float out[4], int* shadow_ray) {
+                    const int32_t* look, int shadow_steps, int liquid, float time, float out[4], int* shadow_ray, o_shrec* rec) {
     orayres R;
     if (shadow_ray) *shadow_ray = 0;
     float dir[3];
     int nrefl;
     float m[3];
-    o_cast_refl(gb, world, org, d0, steps, &R, dir, &nrefl, m, liquid, time);
+    o_events ev;
+    o_cast_refl(gb, world, org, d0, steps, &R, dir, &nrefl, m, liquid, time, rec ? &ev : NULL);
+    if (rec) {
+        rec->R = R;
+        rec->ev = ev;
+        rec->nrefl = nrefl;
+        memcpy(rec->dir, dir, 12);
+        memcpy(rec->mod, m, 12);
+    }
     float c[3];
     if (look && R.pos[0] == look[0] && R.pos[1] == look[1] && R.pos[2] == look[2]) {
         float b[3];
@@ -1563,7 +1597,7 @@ static void* o_shade_worker(void* p) {
         int64_t pi = j->pix ? j->pix[k] : k;
         float d[3];
         o_pixel_dir(j->cam, j->ppx, j->ppy, j->rw, j->rh, (int)(pi % j->W), (int)(pi / j->W), d);
-        o_shade(o_gb_tree, j->t, j->org, d, j->steps, j->sun, j->look, j->shadow_steps, j->liquid, j->time, j->rgba + 4 * k, NULL);
+        o_shade(o_gb_tree, j->t, j->org, d, j->steps, j->sun, j->look, j->shadow_steps, j->liquid, j->time, j->rgba + 4 * k, NULL, NULL);
     }
     return NULL;
 }
@@ -1594,6 +1628,90 @@ EXPORT void orc_shade_frame(const otree* t, const float org[3], const float cam[
     }
     for (int i = 0; i < nthreads; i++) pthread_join(th[i], NULL);
     free(jobs);
+}
+
+/* The shading pass over explicit rays (org[n][3], dir[n][3]), with what orc_shade_frame keeps to itself: per ray the
+   rgba of o_shade and the final record of its primary ray (o_cast_refl: pos, last, steps, hit, axis, t, flags, colour),
+   the final direction and finalColorMod, and the events on the way — reflections, whether it bent, refractive blocks
+   passed, whether the bending block was liquid, the bend's face as 2 * axis + (step < 0) (-1: none), and the
+   reflections before the bend.  Any output may be NULL.  The same o_shade per ray as orc_shade_frame's. */
+typedef struct {
+    const otree* t;
+    const float *org, *dir;
+    float sun[3], time;
+    int steps, shadow_steps, tid, nthreads, liquid;
+    const int32_t* look;
+    int64_t n;
+    float* rgba;
+    int32_t *pos, *last, *stp, *hit, *axis;
+    double* tt;
+    uint32_t* flags;
+    uint64_t* color;
+    int32_t *nrefl, *bent, *tints, *liq_bend, *bend_face, *refl_at_bend;
+    float *dir_out, *mod;
+    int err;
+} o_srjob;
+static void* o_shade_rays_worker(void* p) {
+    o_srjob* j = (o_srjob*)p;
+    for (int64_t k = j->tid; k < j->n; k += j->nthreads) {
+        float rgba[4];
+        o_shrec S;
+        o_shade(o_gb_tree, j->t, j->org + 3 * k, j->dir + 3 * k, j->steps, j->sun, j->look, j->shadow_steps, j->liquid, j->time, rgba,
+                NULL, &S);
+        if (S.R.err) j->err = 1;
+        if (j->rgba) memcpy(j->rgba + 4 * k, rgba, 16);
+        if (j->pos) memcpy(j->pos + 3 * k, S.R.pos, 12);
+        if (j->last) memcpy(j->last + 3 * k, S.R.last, 12);
+        if (j->stp) j->stp[k] = S.R.steps;
+        if (j->hit) j->hit[k] = S.R.hit;
+        if (j->axis) j->axis[k] = S.R.axis;
+        if (j->tt) j->tt[k] = S.R.t;
+        if (j->flags) j->flags[k] = S.R.flags;
+        if (j->color) j->color[k] = S.R.color;
+        if (j->nrefl) j->nrefl[k] = S.nrefl;
+        if (j->bent) j->bent[k] = S.ev.bent;
+        if (j->tints) j->tints[k] = S.ev.tints;
+        if (j->liq_bend) j->liq_bend[k] = S.ev.liq_bend;
+        if (j->bend_face) j->bend_face[k] = S.ev.bent ? 2 * S.ev.bend_axis + (S.ev.bend_sign < 0) : -1;
+        if (j->refl_at_bend) j->refl_at_bend[k] = S.ev.refl_at_bend;
+        if (j->dir_out) memcpy(j->dir_out + 3 * k, S.dir, 12);
+        if (j->mod) memcpy(j->mod + 3 * k, S.mod, 12);
+    }
+    return NULL;
+}
+EXPORT int orc_shade_rays(const otree* t, const float* org, const float* dir, int64_t n, int steps, const float sun[3],
+                          const int32_t* look, int shadow_steps, int liquid, float time, int nthreads, float* rgba, int32_t* pos,
+                          int32_t* last, int32_t* stp, int32_t* hit, int32_t* axis, double* tt, uint32_t* flags, uint64_t* color,
+                          int32_t* nrefl, int32_t* bent, int32_t* tints, int32_t* liq_bend, int32_t* bend_face, int32_t* refl_at_bend,
+                          float* dir_out, float* mod) {
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 256) nthreads = 256;
+    pthread_t th[256];
+    o_srjob* jobs = (o_srjob*)calloc((size_t)nthreads, sizeof(o_srjob));
+    for (int i = 0; i < nthreads; i++) {
+        o_srjob* j = &jobs[i];
+        j->t = t;
+        j->org = org; j->dir = dir;
+        memcpy(j->sun, sun, 12);
+        j->time = time;
+        j->steps = steps; j->shadow_steps = shadow_steps;
+        j->liquid = liquid;
+        j->look = look;
+        j->n = n;
+        j->tid = i; j->nthreads = nthreads;
+        j->rgba = rgba; j->pos = pos; j->last = last; j->stp = stp; j->hit = hit; j->axis = axis; j->tt = tt; j->flags = flags;
+        j->color = color; j->nrefl = nrefl; j->bent = bent; j->tints = tints; j->liq_bend = liq_bend; j->bend_face = bend_face;
+        j->refl_at_bend = refl_at_bend; j->dir_out = dir_out; j->mod = mod;
+        if (nthreads > 1) pthread_create(&th[i], NULL, o_shade_rays_worker, j);
+    }
+    int err = 0;
+    if (nthreads == 1) o_shade_rays_worker(&jobs[0]);
+    for (int i = 0; i < nthreads; i++) {
+        if (nthreads > 1) pthread_join(th[i], NULL);
+        err |= jobs[i].err;
+    }
+    free(jobs);
+    return err ? -1 : 0;
 }
 
 /* §8(d) for the shading pass (bench.py --shade): node entries of every lookup the pass's rays make under
@@ -1656,7 +1774,7 @@ static void* o_shade_entries_worker(void* p) {
         E.t = j->t;
         E.S.stack[0] = j->t->root;
         int sh = 0;
-        o_shade(o_gb_count, &E, j->org, d, j->steps, j->sun, NULL, j->shadow_steps, j->liquid, j->time, rgba, &sh);
+        o_shade(o_gb_count, &E, j->org, d, j->steps, j->sun, NULL, j->shadow_steps, j->liquid, j->time, rgba, &sh, NULL);
         j->out[0] += E.entries;
         j->out[1] += (uint64_t)sh;
         j->out[2] += E.lookups;

@@ -148,6 +148,7 @@ def lib(native=False):
                                   C.c_int, vp, C.c_int, C.c_float]
     L.orc_shade_entries.argtypes = [vp, _f32p, _f32p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, _f32p, C.c_int, vp, C.c_int64,
                                     C.c_int, C.c_int, C.c_float, vp]
+    L.orc_shade_rays.argtypes = [vp, _f32p, _f32p, C.c_int64, C.c_int, _f32p, vp, C.c_int, C.c_int, C.c_float, C.c_int] + [vp] * 17
     L.orc_sin_f32.restype = C.c_float
     L.orc_sin_f32.argtypes = [C.c_float]
     _libs[path] = L
@@ -340,6 +341,27 @@ class Tree:
         self.L.orc_shade_frame(self.h, f3(org), f3(cam), ppx, ppy, W, H, steps, f3(sun), _ptr(look), shadow_steps, _ptr(pix), n, nthreads,
                                _ptr(rgba), 1 if liquid else 0, time)
         return rgba
+
+    def shade_rays(self, org, dirs, steps, sun, look_at=None, shadow_steps=75, liquid=False, time=0.0, nthreads=8):
+        """the shading pass over explicit rays (oracle.c orc_shade_rays; org, dirs: (n, 3) float32): a dict of per-ray arrays —
+        rgba as shade_frame's, the primary ray's final record under the keys test_gpu_parity.compare reads (pos, last, steps,
+        hit, flags, color, t) and axis, the events on its way (nrefl, bent, tints, liq_bend, bend_face = 2 * axis + (step < 0)
+        or -1, refl_at_bend), and the final direction and colour modifier (dir, mod)"""
+        o = np.ascontiguousarray(np.asarray(org, np.float32).reshape(-1, 3))
+        d = np.ascontiguousarray(np.asarray(dirs, np.float32).reshape(-1, 3))
+        assert o.shape == d.shape
+        n = len(o)
+        look = None if look_at is None else np.ascontiguousarray(look_at, dtype=np.int32)
+        out = dict(rgba=np.zeros((n, 4), np.float32), pos=np.zeros((n, 3), np.int32), last=np.zeros((n, 3), np.int32),
+                   steps=np.zeros(n, np.int32), hit=np.zeros(n, np.int32), axis=np.zeros(n, np.int32), t=np.zeros(n, np.float64),
+                   flags=np.zeros(n, np.uint32), color=np.zeros(n, np.uint64), nrefl=np.zeros(n, np.int32), bent=np.zeros(n, np.int32),
+                   tints=np.zeros(n, np.int32), liq_bend=np.zeros(n, np.int32), bend_face=np.zeros(n, np.int32),
+                   refl_at_bend=np.zeros(n, np.int32), dir=np.zeros((n, 3), np.float32), mod=np.zeros((n, 3), np.float32))
+        rc = self.L.orc_shade_rays(self.h, o, d, n, steps, f3(sun), _ptr(look), shadow_steps, 1 if liquid else 0, time, nthreads,
+                                   *[_ptr(v) for v in out.values()])
+        if rc:
+            raise RuntimeError("getBlock hit max depth on a shading ray")
+        return out
 
     def frame_entries(self, org, cam, W, H, steps, ppx=None, ppy=None, pixels=None, nthreads=8):
         if ppx is None:

@@ -21,6 +21,11 @@ void orc_cast_frame_ao(const otree* t, const float* org, const float* cam, float
                        int ao_steps, const int64_t* pix, int64_t n, int nthreads, uint8_t* ao, int32_t* hit);
 void orc_shade_frame(const otree* t, const float* org, const float* cam, float ppx, float ppy, int W, int H, int steps, const float* sun,
                      const int32_t* look, int shadow_steps, const int64_t* pix, int64_t n, int nthreads, float* rgba, int liquid, float time);
+int orc_put_block(otree* t, int x, int y, int z, uint32_t flags, uint64_t color, float meta, int level);
+int orc_shade_rays(const otree* t, const float* org, const float* dir, int64_t n, int steps, const float* sun, const int32_t* look,
+                   int shadow_steps, int liquid, float time, int nthreads, float* rgba, int32_t* pos, int32_t* last, int32_t* stp,
+                   int32_t* hit, int32_t* axis, double* tt, uint32_t* flags, uint64_t* color, int32_t* nrefl, int32_t* bent,
+                   int32_t* tints, int32_t* liq_bend, int32_t* bend_face, int32_t* refl_at_bend, float* dir_out, float* mod);
 int orc_delete_block(otree* t, int x, int y, int z, int level, int ref_shift, uint32_t* f, uint64_t* c, float* m);
 uint64_t orc_frame_entries_ao(const otree* t, const float* org, const float* cam, float ppx, float ppy, int W, int H, int steps, int n_ao,
                               int ao_steps, const int64_t* pix, int64_t n, int nthreads);
@@ -45,6 +50,27 @@ int main(void) {
     orc_shade_frame(t, org, cam, ppx, ppy, W, H, 300, sun, NULL, 75, NULL, N, 2, rgba, 0, 0.0f);
     orc_shade_frame(t, org, cam, ppx, ppy, W, H, 300, sun, NULL, 75, NULL, N, 2, rgba, 1, 1.5f);
     (void)orc_frame_entries_ao(t, org, cam, ppx, ppy, W, H, 300, 16, 5, NULL, N, 2);
+    {
+        /* explicit shading rays with records and event counts: one down onto the reference world's mirror voxel
+           (10, 100, 10), one down through a glass voxel put here */
+        if (orc_put_block(t, 20, 100, 20, 0x4, 12345, 0.0f, 6)) return 1;
+        const float ro[6] = {10.5f, 103.5f, 10.5f, 20.5f, 103.5f, 20.5f}, rd[6] = {0.01f, -1.0f, 0.02f, 0.01f, -1.0f, 0.02f};
+        const int32_t look[3] = {20, 99, 20};
+        float c4[8], dout[6], mod[6];
+        int32_t p2[6], l2[6], s2[2], h2[2], a2[2], nr[2], bt[2], tn[2], lb[2], bf[2], rb[2];
+        double t2[2];
+        uint32_t f2[2];
+        uint64_t c2[2];
+        if (orc_shade_rays(t, ro, rd, 2, 300, sun, look, 75, 1, 0.5f, 2, c4, p2, l2, s2, h2, a2, t2, f2, c2, nr, bt, tn, lb, bf, rb, dout, mod))
+            return 1;
+        if (nr[0] != 1 || bt[0] != 0 || bf[0] != -1 || nr[1] != 0 || bt[1] != 1 || tn[1] < 1 || bf[1] != 3) {
+            printf("shade_rays events: nrefl %d %d bent %d %d tints %d face %d %d\n", nr[0], nr[1], bt[0], bt[1], tn[1], bf[0], bf[1]);
+            return 1;
+        }
+        if (orc_shade_rays(t, ro, rd, 2, 300, sun, NULL, 0, 0, 0.0f, 1, c4, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL,
+                           NULL, NULL, NULL, NULL, NULL))
+            return 1;
+    }
     uint32_t f;
     uint64_t c;
     float m;

@@ -1,9 +1,11 @@
 """GPU parity of the shading pass (svo_shade_rays) against the oracle's restatement
 (oracle.c §shading: low_res.frag's colour model over castRayFromCam hits, reflections on flags&7==3).
 
-Bar: hit records bit-exact (they are the primary cast); lit / shadowed / highlighted / reflected
-colours bit-exact (the same f32 operations in the same order on both sides); sky colours within
-2e-6 absolute (genSkyBox's exp and sqrt: device libm vs host libm may differ in the last ulp)."""
+Bar: lit / shadowed / highlighted / reflected colours bit-exact (the same f32 operations in the same
+order on both sides); sky colours within 2e-6 absolute (genSkyBox's exp and sqrt: device libm vs host
+libm may differ in the last ulp).  The hit records of these frames are only used to split lit from sky
+pixels; the records of reflected and bent rays are compared with the oracle, bit for bit, in
+tests/test_gpu_directed_shading.py."""
 import numpy as np
 import pytest
 

@@ -5,7 +5,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <array>
 #include <string>
 #include <utility>
 #include <vector>
@@ -112,44 +111,6 @@ bool wide_nodes(const svo_tree* t, int32_t flags) { return t->dev_node_cap >= kN
 // The per-lane LDS path of k_cast (Path): 3 dwords per interior depth (levels - 1 of them) per lane of the block
 size_t path_lds(const CastParams& P) { return (size_t)(P.levels > 1 ? P.levels - 1 : 1) * 3 * kBlock * sizeof(uint32_t); }
 
-// The sign-octant instances (dirs 1..8, frame_dirs) of one family, as a table built at compile time: launch block b of the
-// primary casts (AO or not, SEG or not) and of the shading pass's straight trace (with / without hit records) picks its
-// kernel by index instead of a hand-written case per octant
-template <bool AO, bool SHADE, bool SEG, bool NOREC, size_t... I>
-constexpr std::array<CastKernel, sizeof...(I)> octant_kernels(std::index_sequence<I...>) {
-    return {{&k_cast<false, false, AO, SHADE, false, SEG, (int)I + 1, NOREC>...}};
-}
-template <bool AO, bool SHADE, bool SEG, bool NOREC = false>
-void launch_octant(int dirs, dim3 grid, dim3 block, hipStream_t st, const CastParams& P) {
-    static constexpr std::array<CastKernel, 8> tab = octant_kernels<AO, SHADE, SEG, NOREC>(std::make_index_sequence<8>());
-    CastParams arg = P;
-    void* args[] = {&arg};
-    (void)hipLaunchKernel(reinterpret_cast<const void*>(tab[(dirs >= 1 && dirs <= 8 ? dirs : 8) - 1]), grid, block, args, path_lds(P), st);
-}
-template <bool STATS, bool STAMPS, bool AO, bool SHADE>
-void launch_cast(bool wide, bool seg, dim3 grid, dim3 block, hipStream_t st, const CastParams& P, int dirs = 0) {
-    if (!STATS && !STAMPS && !SHADE && !wide && dirs) {  // (narrow trees: below 2^28 nodes)
-        if (seg) launch_octant<AO, false, true>(dirs, grid, block, st, P);
-        else launch_octant<AO, false, false>(dirs, grid, block, st, P);
-        return;
-    }
-    // the camera's octant (the straight trace of the shading rays); without hit records, a launch whose every origin is
-    // exact (seg: need_seg false) takes the straight trace without segment bounds (the bouncing trace keeps them)
-    if (SHADE && !STATS && !wide && dirs) {
-        if (P.pos) launch_octant<false, true, true>(dirs, grid, block, st, P);
-        else if (seg) launch_octant<false, true, true, true>(dirs, grid, block, st, P);
-        else launch_octant<false, true, false, true>(dirs, grid, block, st, P);
-        return;
-    }
-    if (SHADE || seg) {
-        if (wide) hipLaunchKernelGGL((k_cast<STATS, STAMPS, AO, SHADE, true, true>), grid, block, path_lds(P), st, P);
-        else hipLaunchKernelGGL((k_cast<STATS, STAMPS, AO, SHADE, false, true>), grid, block, path_lds(P), st, P);
-    } else {
-        if (wide) hipLaunchKernelGGL((k_cast<STATS, STAMPS, AO, false, true, false>), grid, block, path_lds(P), st, P);
-        else hipLaunchKernelGGL((k_cast<STATS, STAMPS, AO, false, false, false>), grid, block, path_lds(P), st, P);
-    }
-}
-
 // svo_plan.h's launch set-up, from a launch's parameters
 int frame_dirs(const CastParams& P) { return P.mode == MODE_FRAME ? svo::frame_dirs(P.rg, P.width, P.height, P.flags) : 0; }
 bool need_seg(const CastParams& P) {
@@ -159,10 +120,49 @@ bool need_seg(const CastParams& P) {
 void frame_axes(CastParams& P, int dirs) {
     for (int32_t f = 0; dirs && f < P.n_frames; f++) svo::frame_axes(dirs, P.frame_org + 3 * f, P.fax[f].frac, P.fax[f].cell);
 }
+// what decides a launch's instance (svo_plan.h), with the frame set-up of its octant; shade: the shading pass
+svo::CastRequest cast_request(CastParams& P, bool shade, bool wide) {
+    svo::CastRequest q = {};
+    q.stats = (P.flags & SVO_CAST_STATS) != 0;
+    q.timeline = (P.flags & SVO_CAST_TIMELINE) != 0;
+    q.ao = P.ao_n > 0;
+    q.shade = shade;
+    q.records = P.pos != nullptr;
+    q.wide = wide;
+    q.seg = need_seg(P);
+    q.dirs = frame_dirs(P);
+    frame_axes(P, q.dirs);
+    return q;
+}
+
+// Every instance with its template arguments, from the lists that instantiate them; a launch runs the one that
+// svo::cast_instance (svo_plan.h) picks for it
+struct CastEntry {
+    svo::CastInstance inst;
+    CastKernel fn;
+};
+#define SVO_CAST_ENTRY(...) {{__VA_ARGS__}, &k_cast<__VA_ARGS__>},
+const CastEntry kCastTable[] = {SVO_CAST_ALL(SVO_CAST_ENTRY)};
+int launch_cast(const svo::CastRequest& q, dim3 grid, dim3 block, hipStream_t st, const CastParams& P) {
+    const svo::CastInstance k = svo::cast_instance(q);
+    for (const CastEntry& e : kCastTable) {
+        const svo::CastInstance& i = e.inst;
+        if (i.stats != k.stats || i.stamps != k.stamps || i.ao != k.ao || i.shade != k.shade || i.wide != k.wide || i.seg != k.seg ||
+            i.dirs != k.dirs || i.norec != k.norec)
+            continue;
+        CastParams arg = P;
+        void* args[] = {&arg};
+        (void)hipLaunchKernel(reinterpret_cast<const void*>(e.fn), grid, block, args, path_lds(P), st);
+        return SVO_OK;
+    }
+    SVO_FAIL(SVO_EDEVICE, "k_cast: no instance <" + std::to_string(k.stats) + ", " + std::to_string(k.stamps) + ", " + std::to_string(k.ao) + ", " +
+                              std::to_string(k.shade) + ", " + std::to_string(k.wide) + ", " + std::to_string(k.seg) + ", " + std::to_string(k.dirs) +
+                              ", " + std::to_string(k.norec) + "> (svo_cast_instances.h)");
+}
 
 // The two ceiling levels a launch checks, as levels of the tree's table (4^(kCeilK0 + j) columns per block).
 // Primary casts: 16 and 64 columns (C3 0.1824 -> 0.1787 ms, C5 0.562 -> 0.543 against 64 / 256; 16 / 256 was
-// slower than both: profiles/r03/ab_j_*.log).  The shading pass walks every level (trace CEIL 2: P.ceilq); its
+// slower than both: profiles/r03/ab_j_*.log).  The shading pass walks every level (trace T_CEIL_QUADS: P.ceilq); its
 // pair levels are unused.
 constexpr int kCeilPrimary[2] = {0, kCeilPairStep}, kCeilShade[2] = {0, kCeilPairStep};
 // (a launch's second level is read from the pair table, whose high half is level lv[0] + kCeilPairStep: the box of
@@ -404,16 +404,12 @@ extern "C" int svo_shade_rays(const svo_tree* t, const svo_cast_desc* d, const s
     const bool wide = wide_nodes(t, d->flags) || wide_nodes(sc, d->flags);
     std::unique_lock<std::mutex> sched_lock;  // (held from here until the launch and the sort are queued)
     const SchedUse sch = sched_attach(t, d, P, 2, blocks, (hipStream_t)stream, sched_lock);
-    if (P.flags & SVO_CAST_STATS) launch_cast<true, true, false, true>(wide, true, dim3((uint32_t)blocks), dim3(kBlock), (hipStream_t)stream, P);
-    else if (P.flags & SVO_CAST_TIMELINE) launch_cast<false, true, false, true>(wide, true, dim3((uint32_t)blocks), dim3(kBlock), (hipStream_t)stream, P);
-    else {
-        // the straight trace runs on the camera's step octant (frame launches whose every pixel steps with it: frame_dirs;
-        // shaded C3 0.3050 -> 0.2914 ms against generic sign flags, with the shadow rays' sun-octant instances given up
-        // for it: profiles/r05/shade_split_ab.json); its segment bounds only when an origin needs them (0.2887 -> 0.2831)
-        const int dirs = frame_dirs(P);
-        frame_axes(P, dirs);
-        launch_cast<false, false, false, true>(wide, need_seg(P), dim3((uint32_t)blocks), dim3(kBlock), (hipStream_t)stream, P, dirs);
-    }
+    // the straight trace runs on the camera's step octant (frame launches whose every pixel steps with it: frame_dirs;
+    // shaded C3 0.3050 -> 0.2914 ms against generic sign flags, with the shadow rays' sun-octant instances given up
+    // for it: profiles/r05/shade_split_ab.json); its segment bounds only when an origin needs them (0.2887 -> 0.2831)
+    const svo::CastRequest q = cast_request(P, true, wide);
+    rc = launch_cast(q, dim3((uint32_t)blocks), dim3(kBlock), (hipStream_t)stream, P);
+    if (rc) return rc;
     HIP_TRY(hipGetLastError(), SVO_EDEVICE);
     return sched_order(t, sch, (hipStream_t)stream);
 }
@@ -453,20 +449,10 @@ static int cast_launch(const svo_tree* t, const svo_cast_desc* d, const svo_hits
     if (blocks * kBlock > 0xFFFFFFFFll) SVO_FAIL(SVO_ERANGE, "svo_cast_rays: too many rays for one launch");
     const dim3 grid((uint32_t)blocks), block(kBlock);
     hipStream_t st = (hipStream_t)stream;
-    const bool wide = wide_nodes(t, d->flags), seg = need_seg(P);
-    const int dirs = frame_dirs(P);
-    frame_axes(P, dirs);
+    const svo::CastRequest q = cast_request(P, false, wide_nodes(t, d->flags));
     const SchedUse sch = {};  // (primary casts: the default order; see sched_attach)
-    if (P.ao_n > 0) {
-        if (P.flags & SVO_CAST_STATS) launch_cast<true, true, true, false>(wide, seg, grid, block, st, P);
-        else launch_cast<false, false, true, false>(wide, seg, grid, block, st, P, dirs);
-    } else if (P.flags & SVO_CAST_STATS) {
-        launch_cast<true, true, false, false>(wide, seg, grid, block, st, P);
-    } else if (P.flags & SVO_CAST_TIMELINE) {
-        launch_cast<false, true, false, false>(wide, seg, grid, block, st, P);
-    } else {
-        launch_cast<false, false, false, false>(wide, seg, grid, block, st, P, dirs);
-    }
+    rc = launch_cast(q, grid, block, st, P);
+    if (rc) return rc;
     HIP_TRY(hipGetLastError(), SVO_EDEVICE);
     return sched_order(t, sch, st);
 }
@@ -495,7 +481,9 @@ int pick_launch(const svo_tree* t, const float pos[3], const float dir[3], int32
     P.pos = reinterpret_cast<int32_t*>(buf);
     P.t = reinterpret_cast<float*>(reinterpret_cast<char*>(buf) + 16);
     P.info = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(buf) + 20);
-    launch_cast<false, false, false, false>(wide_nodes(t, 0), need_seg(P), dim3(1), dim3(kBlock), stream, P);
+    const svo::CastRequest q = cast_request(P, false, wide_nodes(t, 0));  // (no frame, no octant: dirs 0)
+    const int rc = launch_cast(q, dim3(1), dim3(kBlock), stream, P);
+    if (rc) return rc;
     HIP_TRY(hipGetLastError(), SVO_EDEVICE);
     return SVO_OK;
 }

@@ -14,6 +14,7 @@
 
 #include <type_traits>
 
+#include "svo_cast_instances.h"
 #include "svo_shade.h"
 #include "svo_wire.h"
 
@@ -130,28 +131,30 @@ __global__ __launch_bounds__(kBlock, STATS ? 6 : (SHADE ? (DIRS != 0 ? kShadeWav
         const int32_t esc = (P.pos || look_risk) ? -1 : P.top_scene;
         unsigned long long* const rw = P.stats ? P.stats + SVO_STATS_HEADER + 2 * (int64_t)gridDim.x * (kBlock / 64) + out : nullptr;
         if (STATS || STAMPS) {  // (diagnostics: one trace, bounces included)
-            const Hit h = trace<STATS, true, true, SEG, 0, false, 2, NOREC>(P, mem, P.mats, path, o, d, P.steps, rw, &bn, nullptr, esc, P.top_scene);
+            const Hit h = trace<t_if(STATS, T_STATS) | T_REFLECT | T_ESCAPE | t_if(SEG, T_SEG) | T_CEIL_QUADS | t_if(NOREC, T_NO_T)>(
+                P, mem, P.mats, path, o, d, P.steps, rw, &bn, nullptr, esc, P.top_scene);
             shade_out<0>(P, smem, path, h, bn, out);
         } else {
             // the straight trace to the first block hit — no reflection / refraction upkeep per step, on the camera's step
             // octant (DIRS) — and only a mirror or a refractive block with budget left hands its state on to the bouncing
             // trace, which resumes there (shaded C3 0.3103 -> 0.3027 ms, then 0.2914 with the octant; the straight trace's
             // state on its first hit is the one the bouncing trace from the origin reaches: both take castRayFromCam's
-            // exact steps).  Its column ceilings: the launch's two levels (CEIL 1, as primary casts: 0.8 % faster than the walk
-            // over every level, CEIL 2, which the bouncing trace keeps)
+            // exact steps).  Its column ceilings: the launch's two levels (T_CEIL_PAIRS, as primary casts: 0.8 % faster than
+            // the walk over every level, T_CEIL_QUADS, which the bouncing trace keeps)
             RayState xs;
-            Hit h = trace<false, false, true, SEG, DIRS, false, 1, NOREC, 1>(P, mem, P.mats, path, o, d, P.steps, nullptr, nullptr, nullptr,
-                                                                             esc, P.top_scene, DIRS != 0 ? &P.fax[frm] : nullptr, &xs);
+            Hit h = trace<T_ESCAPE | t_if(SEG, T_SEG) | t_dirs(DIRS) | T_CEIL_PAIRS | t_if(NOREC, T_NO_T) | T_XS_SAVE>(
+                P, mem, P.mats, path, o, d, P.steps, nullptr, nullptr, nullptr, esc, P.top_scene, DIRS != 0 ? &P.fax[frm] : nullptr, &xs);
             const uint32_t mf = ((h.info & HIT_BIT) && h.steps_left > 0) ? P.mat_flags[h.info & MAT_MASK] & 7u : 0u;
             if (mf == 3u || mf == 5u)
-                h = trace<false, true, true, true, 0, false, 2, NOREC, 2>(P, mem, P.mats, path, o, d, P.steps, nullptr, &bn, nullptr, esc,
-                                                                     P.top_scene, nullptr, &xs);
+                h = trace<T_REFLECT | T_ESCAPE | T_SEG | T_CEIL_QUADS | t_if(NOREC, T_NO_T) | T_XS_RESUME>(
+                    P, mem, P.mats, path, o, d, P.steps, nullptr, &bn, nullptr, esc, P.top_scene, nullptr, &xs);
             shade_out<0>(P, smem, path, h, bn, out);
         }
     } else if (out >= 0) {
         Parent pfin;
-        const Hit h = trace<STATS, false, false, SEG, DIRS, AO, 1>(P, mem, P.mats, path, o, d, P.steps, P.stats ? P.stats + SVO_STATS_HEADER + 2 * (int64_t)gridDim.x * (kBlock / 64) + out : nullptr,
-                                   nullptr, AO ? &pfin : nullptr, -1, P.top_solid, DIRS != 0 ? &P.fax[frm] : nullptr);
+        const Hit h = trace<t_if(STATS, T_STATS) | t_if(SEG, T_SEG) | t_dirs(DIRS) | t_if(AO, T_KEEPPAR) | T_CEIL_PAIRS>(
+            P, mem, P.mats, path, o, d, P.steps, P.stats ? P.stats + SVO_STATS_HEADER + 2 * (int64_t)gridDim.x * (kBlock / 64) + out : nullptr,
+            nullptr, AO ? &pfin : nullptr, -1, P.top_solid, DIRS != 0 ? &P.fax[frm] : nullptr);
         if (!SHADE && P.wire) {  // (wave-uniform: one launch writes one kind of record)
             wire_put(P.wire, P.wire_compact != 0, out, o, h.x, h.y, h.z, h.t, h.info);
         } else {
@@ -172,14 +175,14 @@ __global__ __launch_bounds__(kBlock, STATS ? 6 : (SHADE ? (DIRS != 0 ? kShadeWav
                     cnt = ao_count_plan(P, mem, path, pfin, h, l, ax, -st, aol);
                     if (STATS) atomicAdd(P.stats + 22, (unsigned long long)aol);
                 } else {
-                const float ao_o[3] = {(float)lx + 0.5f, (float)ly + 0.5f, (float)lz + 0.5f};
-                for (int32_t i = 0; i < P.ao_n; i++) {
-                    const float hv[3] = {P.ao_tab[3 * i], P.ao_tab[3 * i + 1], P.ao_tab[3 * i + 2]};
-                    float ad[3];
-                    ao_dir(hv, ax, -st, ad);
-                    const Hit a = trace<false>(P, mem, P.mats, path, ao_o, ad, P.ao_steps);
-                    cnt += (a.info & HIT_BIT) ? 1u : 0u;
-                }
+                    const float ao_o[3] = {(float)lx + 0.5f, (float)ly + 0.5f, (float)lz + 0.5f};
+                    for (int32_t i = 0; i < P.ao_n; i++) {
+                        const float hv[3] = {P.ao_tab[3 * i], P.ao_tab[3 * i + 1], P.ao_tab[3 * i + 2]};
+                        float ad[3];
+                        ao_dir(hv, ax, -st, ad);
+                        const Hit a = trace<T_PLAIN>(P, mem, P.mats, path, ao_o, ad, P.ao_steps);
+                        cnt += (a.info & HIT_BIT) ? 1u : 0u;
+                    }
                 }
             }
             P.ao[out] = (uint8_t)cnt;
@@ -197,32 +200,7 @@ __global__ __launch_bounds__(kBlock, STATS ? 6 : (SHADE ? (DIRS != 0 ? kShadeWav
     }
 }
 
-// The instances that exist, by family, as X(STATS, STAMPS, AO, SHADE, WIDE, SEG, DIRS, NOREC) lists: each
-// svo_cast_inst_*.hip defines one family, every other translation unit only declares them (launch_cast, svo_cast.hip).
-// The AO family holds every instance that casts AO rays, its diagnostics included and first: the last instance of a
-// translation unit to use a shared function (ao_count_plan, the AO rays' trace) has it inlined by moving its body
-// instead of copying it, which changes that instance's register allocation — so the instances stay in the order the
-// single translation unit once held them in, where that one was a plain AO instance (tools/isa_identity.py)
-#define SVO_CAST_OCTANTS(X, AO, SHADE, SEG, NOREC)                                                                       \
-    X(false, false, AO, SHADE, false, SEG, 1, NOREC) X(false, false, AO, SHADE, false, SEG, 2, NOREC)                    \
-    X(false, false, AO, SHADE, false, SEG, 3, NOREC) X(false, false, AO, SHADE, false, SEG, 4, NOREC)                    \
-    X(false, false, AO, SHADE, false, SEG, 5, NOREC) X(false, false, AO, SHADE, false, SEG, 6, NOREC)                    \
-    X(false, false, AO, SHADE, false, SEG, 7, NOREC) X(false, false, AO, SHADE, false, SEG, 8, NOREC)
-#define SVO_CAST_GENERIC(X, STATS, STAMPS, AO)  /* no octant: wide / narrow nodes, with / without segments */           \
-    X(STATS, STAMPS, AO, false, true, true, 0, false) X(STATS, STAMPS, AO, false, false, true, 0, false)                 \
-    X(STATS, STAMPS, AO, false, true, false, 0, false) X(STATS, STAMPS, AO, false, false, false, 0, false)
-#define SVO_CAST_SHADE_GENERIC(X, STATS, STAMPS) \
-    X(STATS, STAMPS, false, true, true, true, 0, false) X(STATS, STAMPS, false, true, false, true, 0, false)
-#define SVO_CAST_PRIMARY(X) \
-    SVO_CAST_OCTANTS(X, false, false, true, false) SVO_CAST_OCTANTS(X, false, false, false, false) SVO_CAST_GENERIC(X, false, false, false)
-#define SVO_CAST_AO(X)                                                                                 \
-    SVO_CAST_OCTANTS(X, true, false, true, false) SVO_CAST_OCTANTS(X, true, false, false, false)       \
-    SVO_CAST_GENERIC(X, true, true, true) SVO_CAST_GENERIC(X, false, false, true)
-#define SVO_CAST_SHADING(X) SVO_CAST_OCTANTS(X, false, true, true, false) SVO_CAST_SHADE_GENERIC(X, false, false)
-#define SVO_CAST_SHADING_NOREC(X) SVO_CAST_OCTANTS(X, false, true, true, true) SVO_CAST_OCTANTS(X, false, true, false, true)
-#define SVO_CAST_DIAGNOSTICS(X)                                                                        \
-    SVO_CAST_SHADE_GENERIC(X, true, true) SVO_CAST_GENERIC(X, true, true, false)                       \
-    SVO_CAST_SHADE_GENERIC(X, false, true) SVO_CAST_GENERIC(X, false, true, false)
+// every svo_cast_inst_*.hip defines one family of svo_cast_instances.h, every other translation unit only declares them
 #define SVO_CAST_INSTANCE(...) template __global__ void k_cast<__VA_ARGS__>(const CastParams P);
 #define SVO_CAST_EXTERN(...) extern SVO_CAST_INSTANCE(__VA_ARGS__)
 SVO_CAST_PRIMARY(SVO_CAST_EXTERN)

@@ -81,7 +81,7 @@ struct CastParams {
     uint32_t ceil_sh[2];
     int64_t ceil_off[2];
     const uint32_t* ceilp;  // the launch's two levels paired (svo_tree.d_ceilp at its first level's offset)
-    const uint32_t* sceilp;  // shading: the same pairs of the solid-view tree the shadow rays walk (trace CEIL 3)
+    const uint32_t* sceilp;  // shading: the same pairs of the solid-view tree the shadow rays walk (trace T_CEIL_SHADOW)
     int32_t sceil_levels;
     const uint64_t* ceilq;  // every level per finest block (svo_tree.d_ceilq; trace CEIL == 2)
     uint32_t* guard_trips;  // the tree's counter of progress-guard trips (svo_tree_guard_trips)

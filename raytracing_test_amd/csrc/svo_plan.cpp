@@ -141,6 +141,22 @@ void frame_axes(int dirs, const float org[3], double frac[3], int32_t cell[3]) {
     }
 }
 
+// Diagnostics instances are generic (no octant); an AO launch has its counters but no timeline of its own (TIMELINE
+// alone runs the plain AO instance).  The camera's octant (frame_dirs; a code outside 1..8 counts as 8) is compiled into
+// narrow-node instances only.  Shading instances carry segment bounds — the bouncing trace needs them — except the
+// straight trace of a launch without hit records whose every origin is exact (NOREC without SEG: shaded C3 0.2887 ->
+// 0.2831 ms); shading launches take no AO rays.
+CastInstance cast_instance(const CastRequest& q) {
+    CastInstance k = {q.stats, q.stats || (q.timeline && (q.shade || !q.ao)), q.ao && !q.shade, q.shade, q.wide, q.seg, 0, false};
+    const bool octant = !k.stats && !k.stamps && !q.wide && q.dirs != 0;
+    if (octant) k.dirs = q.dirs >= 1 && q.dirs <= 8 ? q.dirs : 8;
+    if (q.shade) {
+        k.norec = octant && !q.records;
+        k.seg = k.norec ? q.seg : true;
+    }
+    return k;
+}
+
 // The ceiling pairs of level j (its block's ceiling, low 16 bits; its level-(j + kCeilPairStep) block's, high, or the coarsest
 // level's when the tree has fewer) over the blocks holding columns [x0, x1) x [z0, z1) — widened to whole parent blocks, whose change reaches
 // every child's pair.  Returns per level the first and last row written (level j's rows of blocks, row-major [z][x]).

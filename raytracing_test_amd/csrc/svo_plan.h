@@ -15,6 +15,24 @@ int frame_dirs(const RayGen& rg, int32_t width, int32_t height, int32_t flags);
 bool need_seg(int32_t flags, bool explicit_rays, int32_t steps, const float* org, int32_t n_org);
 void frame_axes(int dirs, const float org[3], double frac[3], int32_t cell[3]);
 
+// Which k_cast instance a launch runs: the one place that decides it.  Almost every instance gives identical results, so
+// a wrong pick would only be slower: tests/sanitize/host_sanitize.cpp holds the rule as a table, over every request.
+struct CastRequest {
+    bool stats, timeline;  // SVO_CAST_STATS, SVO_CAST_TIMELINE
+    bool ao;               // the launch casts AO rays
+    bool shade;            // the shading pass
+    bool records;          // (shading) hit records are output
+    bool wide;             // 64-bit node addresses (shading: either tree's)
+    bool seg;              // need_seg
+    int dirs;              // frame_dirs (0: no common octant; the pick ray: 0)
+};
+struct CastInstance {  // k_cast's template arguments, in their order (svo_cast_instances.h)
+    bool stats, stamps, ao, shade, wide, seg;
+    int dirs;
+    bool norec;
+};
+CastInstance cast_instance(const CastRequest& q);
+
 // The host copies of the ceiling tables (svo_tree.ceil_host / ceilp_host / ceilq_host, ceil_off): rebuilt whole from the
 // tree (returns the number of levels), or brought up to date over one rectangle of svo_tree.ceil_dirty, which returns the
 // rows rewritten, first and one past the last: zr per level of the ceilings and pairs, qr of the quads.  Both may throw

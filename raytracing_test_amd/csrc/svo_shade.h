@@ -167,7 +167,7 @@ __device__ __forceinline__ uint32_t ao_count_plan(const CastParams& P, const Mem
 // step octant (0: per-wave sign flags)
 template <int DIRS, class Mem>
 __device__ __forceinline__ void shade_out(const CastParams& P, const Mem& smem, const Path& path, const Hit& h, const Bounce& bn, int64_t out) {
-        if (P.pos) {
+    if (P.pos) {
         reinterpret_cast<int4*>(P.pos)[out] = make_int4(h.x, h.y, h.z, h.steps_left);
         P.t[out] = h.t;
         P.info[out] = h.info;
@@ -212,12 +212,14 @@ __device__ __forceinline__ void shade_out(const CastParams& P, const Mem& smem, 
                 // the reference's sun, normalize(2, 1, 4) (globals.cpp:23; uniform), steps + on every axis: its octant is
                 // compiled into a second copy of the shadow trace (shaded C3 -3.0 %, profiles/r06/ab_sun_octant_shadows.txt);
                 // any other sun takes per-wave sign flags
-                if (DIRS == 0 && P.sun_dirs == 1)
-                    dark = (trace<false, false, true, false, 1, false, 3>(P, smem, P.smats, path, so, P.sun, P.shadow_steps, nullptr, nullptr, nullptr,
-                                                                          P.top_solid).info & HIT_BIT) != 0u;
+                constexpr uint32_t SHADOW = T_ESCAPE | T_CEIL_SHADOW;
+                constexpr int kSunAllPlus = 1;  // (frame_dirs' code of the octant + + +)
+                if (DIRS == 0 && P.sun_dirs == kSunAllPlus)
+                    dark = (trace<SHADOW | t_dirs(kSunAllPlus)>(P, smem, P.smats, path, so, P.sun, P.shadow_steps, nullptr, nullptr, nullptr,
+                                                                P.top_solid).info & HIT_BIT) != 0u;
                 else
-                dark = (trace<false, false, true, false, DIRS, false, 3>(P, smem, P.smats, path, so, P.sun, P.shadow_steps, nullptr, nullptr, nullptr, P.top_solid)
-                            .info & HIT_BIT) != 0u;
+                    dark = (trace<SHADOW | t_dirs(DIRS)>(P, smem, P.smats, path, so, P.sun, P.shadow_steps, nullptr, nullptr, nullptr,
+                                                         P.top_solid).info & HIT_BIT) != 0u;
             }
         }
         if (dark) c = make_float3(col.x * 0.3f * m[0], col.y * 0.3f * m[1], col.z * 0.3f * m[2]);

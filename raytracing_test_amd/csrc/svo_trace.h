@@ -20,7 +20,7 @@
 //    representable multiple of ulp(T); the first crossing at or above B is that exact sum rounded
 //    once, which fma(k, a, T) also computes.  Only later crossings (one more rounding per binade
 //    entered) drift from the closed form, so the crossings are exact segment by segment
-//    (seg_cap), and an empty region is crossed in a few moves (skip_box<true>).
+//    (seg_cap), and an empty region is crossed in a few moves (skip_box with seg).
 // A ray crosses an empty region in O(1): the first event to leave the region is the lexicographic
 // minimum of the three per-axis exit events, and the events before it on the other axes are
 // counted by division (with an exact fix-up).  Rays outside both domains step voxel by voxel
@@ -463,16 +463,23 @@ struct WideNodes {
     }
 };
 
-// SPLIT: the levels above the bricks hold interior nodes or SOLID regions only; a SOLID region ends
-// the ray, so the parent may be overwritten by it, and those levels need no leaf branch and no
-// copies of the loaded node (the shading pass, whose callers read the final parent's regions, keeps
-// the general loop).  PSH (AO instances: ao_count_plan reads the final parent's shift only): a SOLID
-// region above the bricks leaves the shift of its own parent, so no path entry at or below the
-// SOLID node is read back
-template <bool STATS, bool SPLIT, bool PSH, class Mem>
+// lookup()'s compile-time options, one word (lookup<OPT>)
+enum : uint32_t {
+    L_STATS = 1u << 0,  // count into st (diagnostics)
+    // the levels above the bricks hold interior nodes or SOLID regions only; a SOLID region ends the ray, so the parent
+    // may be overwritten by it, and those levels need no leaf branch and no copies of the loaded node (the shading
+    // pass, whose callers read the final parent's regions, keeps the general loop)
+    L_SPLIT = 1u << 1,
+    // (AO instances: ao_count_plan reads the final parent's shift only) a SOLID region above the bricks leaves the shift
+    // of its own parent, so no path entry at or below the SOLID node is read back
+    L_PSH = 1u << 2,
+};
+template <uint32_t OPT, class Mem>
 __device__ __forceinline__ uint32_t lookup(const CastParams& P, const Mem& mem, const Path& path,
                                            const uint32_t w[3], uint32_t moved, Parent& par, uint32_t& sh_out, uint64_t& bmask,
                                            uint32_t& bref, uint32_t& binfo, Stats& st) {
+    static_assert((OPT & ~(L_STATS | L_SPLIT | L_PSH)) == 0u, "lookup: unknown option");
+    constexpr bool STATS = (OPT & L_STATS) != 0u, SPLIT = (OPT & L_SPLIT) != 0u, PSH = (OPT & L_PSH) != 0u;
     uint32_t ni = 0u;
     int32_t dd = 0;
     if (STATS) st.lookups++;
@@ -585,7 +592,6 @@ __device__ __forceinline__ void wrap3(const Ray& R, uint32_t wm, uint32_t w[3]) 
     w[2] = (uint32_t)R.r[2] & wm;
 }
 
-// One ray with castRayFromCam semantics.
 // Voxel steps through a brick on its register mask (see trace): returns the voxel index reached;
 // `left` = per-axis steps left in the brick (bytes 0-2, a zero byte = left the brick), `solid` =
 // stopped on a solid voxel.  The crossing value of every step is kept (recovering it after the
@@ -717,7 +723,7 @@ __device__ __forceinline__ bool ceil_march(const CastParams& P, const uint32_t* 
 }
 
 // A shading ray's DDA state on entering the first block it hits (the cell, crossing values, budget and last step axis):
-// the straight trace before any bounce hands it to the reflection / refraction trace, which resumes from it (trace XS)
+// the straight trace before any bounce hands it to the reflection / refraction trace, which resumes from it (trace: T_XS_SAVE / T_XS_RESUME)
 struct RayState {
     double T[3];
     int32_t r[3];
@@ -753,29 +759,63 @@ __device__ __forceinline__ void refract_dir(float d[3], const float nin[3]) {
     for (int k = 0; k < 3; k++) d[k] = r * d[k] + kf * n[k];
 }
 
-// par_out: receives the parent of the region the ray ended in (it holds the final voxel; the LDS
-// path holds its ancestors at depths 0 .. levels-1-sh/2).  KEEPPAR (AO): only its shift is exact
-// (lookup: PSH) — a ray ending in a SOLID region above the bricks leaves that region's mask and ref
-// ESCAPE (shading rays whose end position is not output): a ray moving up above the highest stored
-// voxel row `top` (wrapped) whose budget cannot carry it past the extent in y leaves the loop as a
-// miss at once — it can only enter empty space — and skips its remaining steps (top < 0: off); so does
-// a ray whose budget ends inside an empty box; and with CEIL, a ray above `top` crosses the whole
-// half-space above it (every x and z) in one move.
-// DIRS (1..8): every ray of the launch steps with the signs dirs_sign(DIRS, k) (frame_dirs proves it
-// on the host): the steps are compile-time constants and the sign branches of the crossings and brick
-// walks fold away; 0: per-wave sign flags (dir_flags)
-// NO_T: no crossing value is output (shading launches without hit records), so none is tracked per step.
-// XS (round 5, the shading pass): 1 — on a hit, store the DDA state the ray entered its block with in *xs (RayState);
-// 2 — start from *xs instead of the origin's first step (the flags fast / lin still from the origin and direction),
-// with no pre-top box and no march: the straight trace of a shading ray hands its first hit on to the bouncing one
 __host__ __device__ constexpr int32_t dirs_sign(int DIRS, int k) { return DIRS == 0 ? 0 : (((DIRS - 1) >> k) & 1) ? -1 : 1; }
 
-template <bool STATS, bool REFLECT = false, bool ESCAPE = false, bool SEG = false, int DIRS = 0, bool KEEPPAR = false, int CEIL = 0,
-          bool NO_T = false, int XS = 0, class Mem>
+// trace()'s compile-time options: one word, trace<OPT>, or-ed from the names below.  Inside trace() each is a constant
+// of the name without its prefix (STATS, REFLECT, ...).
+enum : uint32_t {
+    T_PLAIN = 0u,       // none of them (the AO rays)
+    T_STATS = 1u << 0,  // diagnostics: the traversal counters (Stats), added to P.stats when the ray ends; *ray_work
+    // the shading pass's reflections and refractions, applied where the ray meets such a block (*bounce); the steps'
+    // signs may change on the way
+    T_REFLECT = 1u << 1,
+    // (shading rays whose end position is not output): a ray moving up above the highest stored voxel row `top`
+    // (wrapped) whose budget cannot carry it past the extent in y leaves the loop as a miss at once — it can only enter
+    // empty space — and skips its remaining steps (top < 0: off); so does a ray whose budget ends inside an empty box;
+    // and with column ceilings, a ray above `top` crosses the whole half-space above it (every x and z) in one move.
+    T_ESCAPE = 1u << 2,
+    T_SEG = 1u << 3,  // segment-bounded crossings, for rays that may not be linear (need_seg; see `lin` below)
+    // (AO) of the parent that par_out receives only the shift is exact (lookup: L_PSH) — a ray ending in a SOLID region
+    // above the bricks leaves that region's mask and ref
+    T_KEEPPAR = 1u << 4,
+    // no crossing value is output (shading launches without hit records), so none is tracked per step.
+    T_NO_T = 1u << 5,
+    // The column ceilings the ray checks, at most one of:
+    T_CEIL_NONE = 0u,
+    T_CEIL_PAIRS = 1u << 6,   // the launch's two levels of the column ceilings (P.ceilp pairs)
+    T_CEIL_QUADS = 1u << 7,   // every level, the coarsest block the ray is above (P.ceilq: a max-mipmap walk of the ceilings)
+    T_CEIL_SHADOW = 1u << 8,  // as pairs, on those of the solid-view tree of a shading launch, P.sceilp — the shadow rays
+    T_CEIL_ANY = T_CEIL_PAIRS | T_CEIL_QUADS | T_CEIL_SHADOW,
+    // (the shading pass) the straight trace of a shading ray hands its first hit on to the bouncing one, at most one of:
+    T_XS_NONE = 0u,
+    T_XS_SAVE = 1u << 9,  // on a hit, store the DDA state the ray entered its block with in *xs (RayState)
+    // start from *xs instead of the origin's first step (the flags fast / lin still from the origin and direction), with
+    // no pre-top box and no march
+    T_XS_RESUME = 1u << 10,
+    T_XS_ANY = T_XS_SAVE | T_XS_RESUME,
+    // t_dirs(1..8): every ray of the launch steps with the signs dirs_sign(DIRS, k) (frame_dirs proves it on the host):
+    // the steps are compile-time constants and the sign branches of the crossings and brick walks fold away; 0:
+    // per-wave sign flags (dir_flags)
+    T_DIRS_SHIFT = 11u,
+    T_DIRS_ANY = 15u << T_DIRS_SHIFT,
+};
+__host__ __device__ constexpr uint32_t t_dirs(int dirs) { return (uint32_t)dirs << T_DIRS_SHIFT; }
+__host__ __device__ constexpr uint32_t t_if(bool on, uint32_t opt) { return on ? opt : 0u; }  // an option an instance's flag decides
+
+// One ray with castRayFromCam semantics.  par_out: receives the parent of the region the ray ended in (it holds the
+// final voxel; the LDS path holds its ancestors at depths 0 .. levels-1-sh/2).
+template <uint32_t OPT, class Mem>
 __device__ __forceinline__ Hit trace(const CastParams& P, const Mem& mem, const uint16_t* mats, const Path& path, const float o[3],
                                      const float d[3], int32_t budget, unsigned long long* ray_work = nullptr,
                                      Bounce* bounce = nullptr, Parent* par_out = nullptr, int32_t top = -1, int32_t pre_top = -1,
                                      const FrameAxes* fx = nullptr, RayState* xs = nullptr) {
+    constexpr bool STATS = (OPT & T_STATS) != 0u, REFLECT = (OPT & T_REFLECT) != 0u, ESCAPE = (OPT & T_ESCAPE) != 0u;
+    constexpr bool SEG = (OPT & T_SEG) != 0u, KEEPPAR = (OPT & T_KEEPPAR) != 0u, NO_T = (OPT & T_NO_T) != 0u;
+    constexpr int DIRS = (int)((OPT & T_DIRS_ANY) >> T_DIRS_SHIFT);
+    constexpr uint32_t CEIL = OPT & T_CEIL_ANY, XS = OPT & T_XS_ANY;
+    static_assert((CEIL & (CEIL - 1u)) == 0u, "trace: the T_CEIL_ options exclude each other");
+    static_assert((XS & (XS - 1u)) == 0u, "trace: T_XS_SAVE and T_XS_RESUME exclude each other");
+    static_assert(DIRS <= 8 && (OPT >> (T_DIRS_SHIFT + 4u)) == 0u, "trace: DIRS is 0..8; no other option bits");
     Ray R;
     if (DIRS != 0 && fx) {
         // a frame ray of an octant instance: the origin's part of dda_axis is the frame's (fx)
@@ -832,6 +872,7 @@ __device__ __forceinline__ Hit trace(const CastParams& P, const Mem& mem, const 
     // (T - a on the last step's axis) instead of keeping it on every brick step
     // (NO_T: no crossing value is output — shading launches without hit records — so none is kept)
     constexpr bool TRACK = (REFLECT || SEG) && !NO_T;
+    constexpr uint32_t LOOK = t_if(STATS, L_STATS) | t_if(!REFLECT, L_SPLIT) | t_if(KEEPPAR, L_PSH);  // the region lookups' options
     uint32_t ud[3];
     if (DIRS != 0) {
 #pragma unroll
@@ -845,7 +886,7 @@ __device__ __forceinline__ Hit trace(const CastParams& P, const Mem& mem, const 
     // the hit is mat != kNoHit (a flag of its own costs lane-mask upkeep every iteration)
     uint32_t mat = kNoHit;
     const uint32_t wm = P.wmask;
-    Stats st = {0, 0, 0, 0, 0, 0, {0, 0, 0, 0}, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    Stats st = {};
     Parent par;
     // the root (node 0 of the tree this trace walks; uniform, one scalar load) is the first parent and stands in the
     // per-lane path at depth 0, so the first lookup starts at the root's child slot instead of loading the root (one
@@ -865,10 +906,10 @@ __device__ __forceinline__ Hit trace(const CastParams& P, const Mem& mem, const 
         par.ref = 0u;
         par.sh = 2u * (uint32_t)P.levels;
     }
-    // XS 2: resume a ray from the state its straight trace (XS 1) stopped in — the cell it entered, untested; the
-    // flags above (fast, lin: from the origin and direction) are the ones that trace had
+    // T_XS_RESUME: resume a ray from the state its straight trace (T_XS_SAVE) stopped in — the cell it entered, untested;
+    // the flags above (fast, lin: from the origin and direction) are the ones that trace had
     bool done = R.steps <= 0;
-    if (XS == 2) {
+    if (XS == T_XS_RESUME) {
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             R.T[k] = xs->T[k];
@@ -883,7 +924,7 @@ __device__ __forceinline__ Hit trace(const CastParams& P, const Mem& mem, const 
     // pre_top (>= 0: the tree's highest stored voxel row, tree_top_y): a ray starting above it is in
     // one empty region {y > pre_top} (every x, z; up to the wrap in y) and crosses it in one move,
     // exactly like a box (false: its budget ends up there, state unchanged, the loop walks it)
-    if (XS != 2 && pre_top >= 0 && fast && !done) {
+    if (XS != T_XS_RESUME && pre_top >= 0 && fast && !done) {
         uint32_t w[3];
         wrap3(R, wm, w);
         if ((int32_t)w[1] > pre_top) {
@@ -898,18 +939,15 @@ __device__ __forceinline__ Hit trace(const CastParams& P, const Mem& mem, const 
     // coordinate bits changed since the last voxel known to lie in the parent's region, by ceiling moves since
     // the last lookup and the step before them (the lookup's restart depth)
     uint32_t jump = 0u;
-    // CEIL 1: the launch's two levels of the column ceilings (P.ceilp pairs); 2: every level, the coarsest block the ray is
-    // above (P.ceilq: a max-mipmap walk of the ceilings); 3: as 1 on P.sceilp
-    // (CEIL 3: CEIL 1 on the pairs of the solid-view tree of a shading launch, P.sceilp — the shadow rays)
-    const bool ceil_on = CEIL != 0 && (CEIL == 3 ? P.sceil_levels : P.ceil_levels) > 0;  // (uniform)
-    const uint32_t* const ceilp = CEIL == 3 ? P.sceilp : P.ceilp;
+    const bool ceil_on = CEIL != T_CEIL_NONE && (CEIL == T_CEIL_SHADOW ? P.sceil_levels : P.ceil_levels) > 0;  // (uniform)
+    const uint32_t* const ceilp = CEIL == T_CEIL_SHADOW ? P.sceilp : P.ceilp;
     uint32_t ckey = 0xFFFFFFFFu, cval = 0u;  // the lane's 16-column block (key) and its ceilings (c0 | c1 << 16)
-    uint64_t cq = 0ull;                      // (CEIL 2: the ceilings of the blocks of every level holding the lane's 16-column block)
+    uint64_t cq = 0ull;                      // (T_CEIL_QUADS: the ceilings of the blocks of every level holding the lane's 16-column block)
     // the descent through the air above the terrain in one march (ceil_march): linear primary / AO rays stepping down
     // (the voxel it ends in is untested, even when the budget ends with it: the loop tests it)
     // (primary / AO casts, and the shading pass's rays before any bounce; exact-sum lanes only: `lin` in segment instances)
-    constexpr bool MARCH = CEIL == 1 || CEIL == 2;
-    if (XS != 2 && MARCH && ceil_on && !done && (SEG ? lin : fast) && R.s[1] < 0 && R.steps > 0) {
+    constexpr bool MARCH = CEIL == T_CEIL_PAIRS || CEIL == T_CEIL_QUADS;
+    if (XS != T_XS_RESUME && MARCH && ceil_on && !done && (SEG ? lin : fast) && R.s[1] < 0 && R.steps > 0) {
         int32_t ex[3];
         if (ceil_march<STATS>(P, ceilp, R, wm, ex, st)) (void)skip_box<TRACK, RB>(R, ex, wseg);
     }
@@ -940,8 +978,8 @@ __device__ __forceinline__ Hit trace(const CastParams& P, const Mem& mem, const 
         int32_t cex[3] = {0, 0, 0};
         bool cl = false, any_cl = false, gt = false;
         int32_t c0 = -1, c1 = 32767;  // the ceilings of the lane's blocks at the launch's two levels (set_ceilings)
-        uint32_t lv = 0u;             // (CEIL 2) how many levels' ceilings the ray is above: its box is a block of level lv - 1
-        if (CEIL == 2 && ceil_on && fast && R.steps > 0) {
+        uint32_t lv = 0u;             // (T_CEIL_QUADS) how many levels' ceilings the ray is above: its box is a block of level lv - 1
+        if (CEIL == T_CEIL_QUADS && ceil_on && fast && R.steps > 0) {
             const int32_t y = (int32_t)w[1];
             constexpr uint32_t lsh0 = 2u * kCeilK0;
             const uint32_t rows0 = (wm + 1u) >> lsh0;
@@ -982,7 +1020,7 @@ __device__ __forceinline__ Hit trace(const CastParams& P, const Mem& mem, const 
             const bool p1 = y > c1;
             uint32_t bmk = (1u << (p1 ? P.ceil_sh[1] : P.ceil_sh[0])) - 1u;  // block width - 1
             int32_t c = p1 ? c1 : c0;
-            if (CEIL == 2) {
+            if (CEIL == T_CEIL_QUADS) {
                 const uint32_t l = (lv - 1u) & 3u;  // (lanes with lv 0 take no box)
                 bmk = (1u << (2u * (kCeilK0 + l))) - 1u;
                 c = (int32_t)(int16_t)(cq >> (16u * l));
@@ -995,7 +1033,7 @@ __device__ __forceinline__ Hit trace(const CastParams& P, const Mem& mem, const 
         }
         uint32_t kind = R_CEIL;
         if (!cl) {
-            kind = lookup<STATS, !REFLECT, KEEPPAR>(P, mem, path, w, moved, par, sh, bmask, bref, binfo, st);
+            kind = lookup<LOOK>(P, mem, path, w, moved, par, sh, bmask, bref, binfo, st);
             jump = 0u;
         }
         if (kind == R_SOLID) {
@@ -1229,7 +1267,7 @@ __device__ __forceinline__ Hit trace(const CastParams& P, const Mem& mem, const 
         }
     }
     if (par_out) *par_out = par;
-    if (XS == 1 && hit) {
+    if (XS == T_XS_SAVE && hit) {
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             xs->T[k] = R.T[k];

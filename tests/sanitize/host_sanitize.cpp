@@ -3,7 +3,8 @@
 // tests/test_sanitizers.py from raytracing_test_amd/csrc/svo_world.cpp: world edits, every builder in
 // both views, incremental updates (patch, growth, rebuild), lookups, export and the checkpoint round trip;
 // and from svo_plan.cpp, the launch planning: the frame octant, the segment test, the ceiling tables kept up
-// to date over edits, the AO plan image, the sync bookkeeping and the frame schedule's decisions.
+// to date over edits, the AO plan image, the sync bookkeeping, the frame schedule's decisions and the choice of the
+// cast kernel's instance.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -12,6 +13,7 @@
 #include <vector>
 
 #include "../../include/svo_rt.h"
+#include "../../raytracing_test_amd/csrc/svo_cast_instances.h"
 #include "../../raytracing_test_amd/csrc/svo_plan.h"
 
 // the device half of the library (the .hip files; svo_tree_destroy: svo_device.hip) is not built here: a tree is only ever host-side
@@ -189,6 +191,79 @@ static void check_schedule() {
     EXPECT(!p.use_order && p.sort);
 }
 
+// Which k_cast instance a launch runs (svo::cast_instance) against the rule written out as rows, over every request; the
+// results are exactly the instances that exist (svo_cast_instances.h: the lists the kernels are instantiated from).
+// A row: the request fields it holds for (ANY: every value; dirs: ANY, 0 or NZ, any octant), then the instance (REQ: the
+// request's field of that name).  Every request must fall under exactly one row.
+enum { ANY = -1, REQ = -1, NZ = 1 };
+struct InstanceRule {
+    int stats, timeline, ao, shade, records, wide, dirs;  // (seg: ANY in every row)
+    int STATS, STAMPS, AO, SHADE, WIDE, SEG, DIRS, NOREC;
+};
+static const InstanceRule kInstanceRules[] = {
+    // stats timeline ao shade records wide dirs    STATS STAMPS AO SHADE WIDE SEG DIRS NOREC
+    // primary and AO casts, the pick ray: counters bring the stamps; an AO launch has no timeline of its own
+    {1, ANY, ANY, 0, ANY, ANY, ANY, /**/ 1, 1, REQ, 0, REQ, REQ, 0, 0},
+    {0, 1, 0, 0, ANY, ANY, ANY, /**/ 0, 1, 0, 0, REQ, REQ, 0, 0},
+    {0, ANY, 1, 0, ANY, 0, ANY, /**/ 0, 0, 1, 0, 0, REQ, REQ, 0},  // (the octant: narrow nodes only)
+    {0, ANY, 1, 0, ANY, 1, ANY, /**/ 0, 0, 1, 0, 1, REQ, 0, 0},
+    {0, 0, 0, 0, ANY, 0, ANY, /**/ 0, 0, 0, 0, 0, REQ, REQ, 0},
+    {0, 0, 0, 0, ANY, 1, ANY, /**/ 0, 0, 0, 0, 1, REQ, 0, 0},
+    // shading: diagnostics
+    {1, ANY, ANY, 1, ANY, ANY, ANY, /**/ 1, 1, 0, 1, REQ, 1, 0, 0},
+    {0, 1, ANY, 1, ANY, ANY, ANY, /**/ 0, 1, 0, 1, REQ, 1, 0, 0},
+    // shading on the camera's octant: with hit records, without
+    {0, 0, ANY, 1, 1, 0, NZ, /**/ 0, 0, 0, 1, 0, 1, REQ, 0},
+    {0, 0, ANY, 1, 0, 0, NZ, /**/ 0, 0, 0, 1, 0, REQ, REQ, 1},
+    // shading otherwise: wide nodes, or no common octant
+    {0, 0, ANY, 1, ANY, 1, ANY, /**/ 0, 0, 0, 1, 1, 1, 0, 0},
+    {0, 0, ANY, 1, ANY, 0, 0, /**/ 0, 0, 0, 1, 0, 1, 0, 0},
+};
+
+static bool same_instance(const svo::CastInstance& a, const svo::CastInstance& b) {
+    return a.stats == b.stats && a.stamps == b.stamps && a.ao == b.ao && a.shade == b.shade && a.wide == b.wide && a.seg == b.seg &&
+           a.dirs == b.dirs && a.norec == b.norec;
+}
+
+static void check_cast_instances() {
+#define LISTED(...) {__VA_ARGS__},
+    const std::vector<svo::CastInstance> listed = {SVO_CAST_ALL(LISTED)};
+#undef LISTED
+    std::vector<int> picked(listed.size(), 0);
+    for (size_t i = 0; i < listed.size(); i++)
+        for (size_t j = 0; j < i; j++) EXPECT(!same_instance(listed[i], listed[j]));
+    const auto holds = [](int rule, int v) { return rule == ANY || rule == v; };
+    const auto pick = [](int rule, int req) { return rule == REQ ? req : rule; };
+    for (int bits = 0; bits < 128; bits++)
+        for (int dirs = 0; dirs <= 8; dirs++) {
+            const svo::CastRequest q = {(bits & 1) != 0,  (bits & 2) != 0,  (bits & 4) != 0,  (bits & 8) != 0,
+                                        (bits & 16) != 0, (bits & 32) != 0, (bits & 64) != 0, dirs};
+            const svo::CastInstance k = svo::cast_instance(q);
+            int rules = 0;
+            for (const InstanceRule& r : kInstanceRules) {
+                if (!(holds(r.stats, q.stats) && holds(r.timeline, q.timeline) && holds(r.ao, q.ao) && holds(r.shade, q.shade) &&
+                      holds(r.records, q.records) && holds(r.wide, q.wide) && holds(r.dirs, dirs != 0)))
+                    continue;
+                rules++;
+                const svo::CastInstance want = {r.STATS != 0, r.STAMPS != 0, pick(r.AO, q.ao) != 0, r.SHADE != 0, pick(r.WIDE, q.wide) != 0,
+                                                pick(r.SEG, q.seg) != 0, pick(r.DIRS, dirs), r.NOREC != 0};
+                EXPECT(same_instance(k, want));
+            }
+            EXPECT(rules == 1);
+            size_t at = 0;
+            while (at < listed.size() && !same_instance(listed[at], k)) at++;
+            EXPECT(at < listed.size());
+            picked[at]++;
+        }
+    for (size_t i = 0; i < listed.size(); i++) EXPECT(picked[i] > 0);
+    // an octant code outside 1..8 counts as 8
+    svo::CastRequest q = {};
+    q.dirs = 9;
+    EXPECT(svo::cast_instance(q).dirs == 8);
+    q.dirs = -1;
+    EXPECT(svo::cast_instance(q).dirs == 8);
+}
+
 static void probe(const svo_tree* t, int n, unsigned seed) {
     std::vector<int32_t> xyz(3 * n);
     for (int i = 0; i < 3 * n; i++) xyz[i] = (int32_t)((seed = seed * 1103515245u + 12345u) >> 8) % 2048 - 512;
@@ -266,6 +341,7 @@ int main(int argc, char** argv) {
     check_ao_plan(16, 128, false);
     check_ao_plan(65, 4, false);
     check_schedule();
+    check_cast_instances();
     // error paths return codes (no exits, no leaks)
     svo_world* bad = nullptr;
     if (svo_world_create(9, &bad) == 0) return 1;

@@ -429,3 +429,113 @@ def ref_noise_batch(seed, x, y):
     out = np.zeros(len(x), np.float64)
     L.ref_noise2_batch(seed, x, y, out, len(x))
     return out
+
+
+# ---------------------------------------------------------------------------------------------- the compiled reference core --
+REF_CORE = os.path.join(HERE, "_ref", "ref_core")
+_REF_OPS = dict(init=1, clean=2, gen=3, put=4, get=5, delete=6, cast=7, pools=8, root=9, box=10)  # ref_core_driver.cpp's OP_*
+_REF_CMD_WORDS, _REF_RES_WORDS = 10, 12
+
+
+class RefCoreError(RuntimeError):
+    """the reference process ended abnormally (status: its exit code, or minus the signal's number)"""
+
+    def __init__(self, status, stderr):
+        RuntimeError.__init__(self, "ref_core ended with status %d: %s" % (status, stderr.strip()[-300:]))
+        self.status = status
+
+
+def _ref_block(w):
+    """(n, 4) result words -> getBlock's Block as arrays"""
+    return dict(flags=w[:, 0].copy(), color=w[:, 1].astype(np.uint64) | (w[:, 2].astype(np.uint64) << np.uint64(32)),
+                meta=w[:, 3].copy().view(np.float32))
+
+
+def ref_core_run(commands, timeout=120):
+    """Run a command list through the reference's own compiled code (oracle/_ref/ref_core: ref_core_driver.cpp over
+    the reference's tree, allocator, genWorld and castRayFromCam; REFERENCE_PINS.md) in a fresh child process — one
+    process is one world — and return one result per command.  None when the program has not been built; RefCoreError
+    with the exit status when the process ends abnormally.  Commands (tuples):
+        ("init",)  ("clean",)  ("gen",)                       -> None
+        ("put", points (n, 3), flags, colours, level[, meta]) -> None       n putBlock calls, in order
+        ("get", points (n, 3))                                -> dict(flags, color, meta)
+        ("delete", (x, y, z), level)                          -> dict(flags, color, meta) of the returned Block, length 1
+        ("cast", origins (n, 3) f32, dirs (n, 3) f32, steps)  -> dict(pos, last, steps, flags, color, meta): RayResult and
+                                                                 getBlock(pos); steps an int or (n,); last is 0 where steps is 0
+        ("pools",)   -> dict(node_next, array_next, node_free, array_free, nodes, arrays): allocation indices in bytes,
+                        free-list populations, and the indices as counts (16 B nodes, 256 B child arrays)
+        ("root",)    -> dict(flags, bitmap, children)
+        ("box", (x0, y0, z0), (nx, ny, nz))  -> dict(flags, color) of shape (nz, ny, nx): getBlock over the box"""
+    import tempfile
+
+    if not os.path.exists(REF_CORE):
+        return None
+    words, spans = [], []
+    for c in commands:
+        op = _REF_OPS[c[0]]
+        if c[0] in ("put", "get"):
+            p = np.asarray(c[1], np.int64).reshape(-1, 3)
+        elif c[0] in ("delete", "box"):
+            p = np.asarray(c[1], np.int64).reshape(1, 3)
+        elif c[0] == "cast":
+            p = np.ascontiguousarray(np.asarray(c[1], np.float32).reshape(-1, 3)).view(np.uint32)
+        else:
+            p = np.zeros((1, 3), np.int64)
+        w = np.zeros((len(p), _REF_CMD_WORDS), np.uint32)
+        w[:, 0] = op
+        w[:, 1:4] = p.astype(np.int32).view(np.uint32) if p.dtype != np.uint32 else p
+        if c[0] == "put":
+            col = np.broadcast_to(np.asarray(c[3], np.uint64), (len(p),))
+            w[:, 4] = c[4]
+            w[:, 5] = np.broadcast_to(np.asarray(c[2], np.uint32), (len(p),))
+            w[:, 6] = (col & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+            w[:, 7] = (col >> np.uint64(32)).astype(np.uint32)
+            w[:, 8] = np.broadcast_to(np.asarray(c[5] if len(c) > 5 else 0.0, np.float32), (len(p),)).copy().view(np.uint32)
+        elif c[0] == "delete":
+            w[:, 4] = c[2]
+        elif c[0] == "box":
+            w[0, 4:7] = c[2]
+        elif c[0] == "cast":
+            d = np.ascontiguousarray(np.asarray(c[2], np.float32).reshape(-1, 3)).view(np.uint32)
+            assert d.shape == p.shape
+            s = np.broadcast_to(np.asarray(c[3], np.int64), (len(p),))
+            assert (s >= 0).all() and (s < 2 ** 31).all()
+            w[:, 4:7] = d
+            w[:, 7] = s.astype(np.uint32)
+        a = spans[-1][1] if spans else 0
+        spans.append((a, a + len(p) * _REF_RES_WORDS + (3 * int(np.prod(c[2])) if c[0] == "box" else 0)))
+        words.append(w)
+    with tempfile.TemporaryDirectory(prefix="ref_core_") as tmp:
+        fin, fout = os.path.join(tmp, "commands.bin"), os.path.join(tmp, "results.bin")
+        np.concatenate(words).astype("<u4").tofile(fin) if words else open(fin, "wb").close()
+        r = subprocess.run([REF_CORE, fin, fout], stdin=subprocess.DEVNULL, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE,
+                           timeout=timeout, text=True, errors="replace")
+        if r.returncode != 0:
+            raise RefCoreError(r.returncode, r.stderr)
+        res = np.fromfile(fout, "<u4")
+    assert len(res) == (spans[-1][1] if spans else 0)
+    out = []
+    for c, (a, b) in zip(commands, spans):
+        if c[0] == "box":
+            nx, ny, nz = (int(v) for v in c[2])
+            assert res[a] == _REF_OPS["box"] and res[a + 1] == nx * ny * nz
+            v = res[a + _REF_RES_WORDS:b].reshape(nz, ny, nx, 3)
+            out.append(dict(flags=v[..., 0].copy(), color=v[..., 1].astype(np.uint64) | (v[..., 2].astype(np.uint64) << np.uint64(32))))
+            continue
+        w = res[a:b].reshape(-1, _REF_RES_WORDS)
+        assert (w[:, 0] == _REF_OPS[c[0]]).all()
+        if c[0] in ("get", "delete"):
+            out.append(_ref_block(w[:, 1:5]))
+        elif c[0] == "cast":
+            d = _ref_block(w[:, 8:12])
+            d.update(pos=w[:, 1:4].copy().view(np.int32), last=w[:, 4:7].copy().view(np.int32), steps=w[:, 7].copy().view(np.int32))
+            out.append(d)
+        elif c[0] == "pools":
+            v = [int(x) for x in w[0, 1:5].view(np.int32)]
+            out.append(dict(node_next=int(w[0, 1]), array_next=int(w[0, 2]), node_free=v[2], array_free=v[3],
+                            nodes=int(w[0, 1]) >> 4, arrays=int(w[0, 2]) >> 8))
+        elif c[0] == "root":
+            out.append(dict(flags=int(w[0, 1]), bitmap=int(w[0, 2]) | (int(w[0, 3]) << 32), children=int(w[0, 4])))
+        else:
+            out.append(None)
+    return out

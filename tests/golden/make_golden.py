@@ -10,10 +10,15 @@ Sources (all reference-produced, none from this repo's code):
   * hemisphere_ref.json — stdout of /root/reference/gen_hemisphare_distrib.py (N = 20, run with
                         MPLBACKEND=Agg), plus the 20 literals of src/shaders/light_scattering.frag:
                         134-153 as DATA (the float32 table the shader uses).
-  * reference_facts.json — values the survey recorded by compiling and running the reference's own
-                        C++: test.cpp's known answer, the reference world's
-                        node / array counts, root bitmap, wrap and max-depth behaviour, the pick ray
-                        and the frame statistics at the default camera.
+  * reference_facts.json — the reference world's node / array counts, root bitmap, wrap equality and the pick ray
+                        from oracle/_ref/ref_core (the reference's tree, genWorld and castRayFromCam compiled from
+                        where they lie: oracle/REFERENCE_PINS.md); the rest as the survey recorded it by compiling
+                        and running the reference's own C++: test.cpp's known answer,
+                        the max-depth behaviour and the frame statistics at the default camera.
+  * pins_R.npz, pins_P.npz — lookups, ray batteries and pixel fans on the reference world and on the pin world
+                        (tests/pin_world.py), inputs and the answers of oracle/_ref/ref_core (tests/pin_cases.py
+                        says what a file holds).  Data only.  The generator fails, and writes nothing, unless every
+                        reference process exits 0 with an empty array free list; no probe or ray is left out.
 """
 import json
 import os
@@ -80,9 +85,54 @@ def hemisphere():
               open(os.path.join(HERE, "hemisphere_ref.json"), "w"), indent=1)
 
 
+def pins():
+    """pins_R.npz / pins_P.npz: see tests/pin_cases.py"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pin_cases as pc
+    from oracle import oracle as O
+
+    O.build_ref()
+    out = {}
+    for world in ("R", "P"):
+        inp = pc.make_inputs(world, O, pc.FIXTURE_SEED[world], pc.FIXTURE_PROBES, pc.FIXTURE_RANDOM)
+        got = pc.reference_records(O, world, inp)  # (raises unless the process exits 0)
+        assert got is not None, "oracle/_ref/ref_core was not built: are the reference's sources here?"
+        rec, pools, root = got
+        assert len(rec["probe_flags"]) == len(inp["probes"]) and len(rec["ray_steps"]) == len(inp["ray_org"])  # nothing left out
+        assert len(rec["frame_steps"]) == len(inp["frame_budget"]) * pc.FRAME_W * pc.FRAME_H
+        out[world] = pc.pack(inp, rec, pools, root)
+    for world, arrays in out.items():
+        path = os.path.join(HERE, "pins_%s.npz" % world)
+        pc.save_npz(path, arrays)
+        assert os.path.getsize(path) <= 256 * 1024, path
+        print("%s: %d probes, %d rays, %d frame rays, %d bytes" % (os.path.basename(path), len(arrays["probes"]), len(arrays["ray_org"]),
+                                                                 len(arrays["frame_pos"]), os.path.getsize(path)))
+
+
+def ref_core_facts():
+    """what oracle/_ref/ref_core says about the reference world: pool counts, root bitmap, wrap, the pick ray"""
+    from oracle import oracle as O
+
+    O.build_ref()
+    a, b = [1034, 5, 10], [10, 5, 10]
+    org, d = [35, 50, 35], [1, 0, 1]
+    res = O.ref_core_run([("init",), ("gen",), ("pools",), ("root",), ("get", [a, b]), ("cast", [org], [O.normalize(d)], 30)])
+    assert res is not None, "oracle/_ref/ref_core was not built: are the reference's sources here?"
+    pools, root, g, ray = res[2:]
+    assert pools["node_free"] == 0 and pools["array_free"] == 0
+    step = ray["pos"][0] - ray["last"][0]
+    assert sorted(np.abs(step).tolist()) == [0, 0, 1]
+    return {"reference_world": {"nodes": pools["nodes"], "arrays": pools["arrays"], "root_bitmap": "0x%016x" % root["bitmap"],
+                                "source": "oracle/_ref/ref_core: initTetraHexaTree + genWorld, allocation indices / 16 and / 256"},
+            "wrap": {"a": a, "b": b, "equal": bool(g["flags"][0] == g["flags"][1] and g["color"][0] == g["color"][1] and g["color"][0] != 2 ** 64 - 1),
+                     "source": "oracle/_ref/ref_core: getBlock at both (a stored block)"},
+            "pick_ray_default_camera": {"origin": org, "dir_unnormalized": d, "walks_axis": int(np.abs(step).argmax()),
+                                        "source": "oracle/_ref/ref_core: castRayFromCam(30), the axis of pos - lastPos"}}
+
+
 def facts():
     f = {
-        "provenance": "SURVEY.md probes: the reference C++ (tetrahexa_tree.cpp, voxel_allocator.cpp, world_gen.cpp, "
+        "provenance": "oracle/_ref/ref_core where an entry's source says so; otherwise SURVEY.md probes: the reference C++ (tetrahexa_tree.cpp, voxel_allocator.cpp, world_gen.cpp, "
                       "ray_caster.cpp, OpenSimplexNoise.cpp, test.cpp) compiled and run in the survey container",
         "test_cpp_kat": {"dir_unnormalized": [11, 20, 3], "origin": [10.5, 12.1, 14.7], "steps": 500,
                          "last_hit": 1, "round": [172, 306, 58], "source": "SURVEY.md §4 (test.cpp:78-134)"},
@@ -98,6 +148,7 @@ def facts():
                                  "mean_dda_steps": 169.8, "tolerance": [0.0005, 0.05], "source": "SURVEY.md §6"},
         "terrain_4096_height_range": {"min": 1, "max": 63, "source": "SURVEY.md §7 (hard parts: scale)"},
     }
+    f.update(ref_core_facts())
     json.dump(f, open(os.path.join(HERE, "reference_facts.json"), "w"), indent=1)
 
 
@@ -106,4 +157,5 @@ if __name__ == "__main__":
     noise_live()
     hemisphere()
     facts()
+    pins()
     print("golden vectors written to", HERE)

@@ -2,7 +2,7 @@
 //
 // genWorld's column tops (world_gen.cpp:22, OpenSimplex 2D from include/OpenSimplexNoise.cpp:77-208)
 // are evaluated one column per lane, then the same canonical breadth-first tree the host terrain
-// builder emits (svo_world.cpp build_from_heights) is built level by level on the GPU:
+// builder emits (svo_terrain.cpp build_from_heights) is built level by level on the GPU:
 //   * a min/max height pyramid over aligned 4^k column footprints classifies any aligned region
 //     in O(1) (EMPTY / uniform SOLID / MIXED, the host's classify_region);
 //   * one wavefront per region, one lane per child slot (or per voxel at the brick level):
@@ -38,7 +38,7 @@ struct DevTerrain {
     uint32_t id_of[5];
     int32_t view;  // SVO_VIEW_SOLID / SVO_VIEW_ALL
 
-    // svo_world.cpp classify_region: class of the aligned region [x0,x0+s)x[y0,y0+s)x[z0,z0+s), s = 4^k
+    // svo_terrain.cpp classify_region: class of the aligned region [x0,x0+s)x[y0,y0+s)x[z0,z0+s), s = 4^k
     __device__ uint32_t classify(int32_t x0, int32_t y0, int32_t z0, int32_t s, int k) const {
         const int32_t y1 = y0 + s - 1;
         if (x0 >= W || z0 >= L) return G_EMPTY;

@@ -6,7 +6,7 @@
 //   uint32_t S::voxel(x, y, z)               the palette id stored at a voxel (G_EMPTY: none)
 // One wavefront per region, one lane per child slot (or per voxel at the brick level): ballots give the child mask,
 // the MIXED children and the stored voxels; exclusive scans over the regions (hipCUB) place every child block and
-// material run; a second pass writes them.  The output is the host's canonical linearisation (svo_world.cpp
+// material run; a second pass writes them.  The output is the host's canonical linearisation (svo_linearise.cpp
 // svo_build_view) byte for byte, left in HBM and adopted as the tree's uploaded copy.
 #pragma once
 

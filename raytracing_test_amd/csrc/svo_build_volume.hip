@@ -5,7 +5,7 @@
 //   * class pyramid, bottom up, over the world-aligned bounding box of the volume: level 1 holds one 16-bit class word
 //     per world-aligned 4^3 brick — C_EMPTY, an id (all 64 voxels that one in-view id) or C_MIXED — and levels 2..levels
 //     fold 64 child classes each (all equal and not MIXED: that class; else MIXED; children outside the box are EMPTY:
-//     svo_world.cpp fold_classes).  Level 1 reads the whole volume once and is the memory-bound pass: a block takes a
+//     svo_world.h fold_classes).  Level 1 reads the whole volume once and is the memory-bound pass: a block takes a
 //     strip of 128 bricks along x of one (y, z) brick row; a lane loads 8 consecutive voxels (16 B at any even address,
 //     two bricks) of two of the strip's 16 rows, 8 neighbouring lanes read 128 contiguous bytes of a row, and the 8
 //     lanes holding the 16 rows of the same two bricks (8, 16 and 32 lanes apart) fold their class words by three lane

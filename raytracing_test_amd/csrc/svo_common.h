@@ -1,4 +1,4 @@
-// svo_common.h — definitions shared by the host builder (svo_world.cpp) and the gfx950 kernels
+// svo_common.h — definitions shared by the host builders (svo_linearise.cpp, svo_terrain.cpp) and the gfx950 kernels
 // (svo_cast_kernel.h).  Everything arithmetic here is compiled with -ffp-contract=off on both sides and
 // rounds identically on x86-64 and gfx950: float divisions and square roots go through double
 // precision and are rounded once to float (double rounding is innocuous for +,-,*,/,sqrt when the

@@ -7,12 +7,6 @@
 
 #include "svo_internal.h"
 
-#define SVO_FAIL(code, msg)     \
-    do {                        \
-        svo::set_error(msg);    \
-        return (code);          \
-    } while (0)
-
 #define HIP_TRY(expr, code)                                                                    \
     do {                                                                                       \
         hipError_t e_ = (expr);                                                                \

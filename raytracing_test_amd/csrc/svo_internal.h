@@ -1,5 +1,6 @@
-// svo_internal.h — host-side object layouts shared by svo_world.cpp and svo_plan.cpp (builders and launch
-// planning, C++ host) and the HIP translation units (device residency, launches).  Not part of the public ABI (include/svo_rt.h).
+// svo_internal.h — host-side object layouts shared by the C++ host files (svo_world.cpp, svo_linearise.cpp,
+// svo_terrain.cpp: the world and the builders; svo_tree.cpp, svo_tree_file.cpp: queries and checkpoints; svo_plan.cpp:
+// launch planning) and the HIP translation units (device residency, launches).  Not part of the public ABI (include/svo_rt.h).
 #pragma once
 
 #include <stdint.h>
@@ -28,7 +29,16 @@ inline bool material_solid(const Material& m) {
 // stored by a tree of `view` (SVO_VIEW_SOLID: what castRayFromCam hits; SVO_VIEW_ALL: every block)
 inline bool material_in_view(const Material& m, int32_t view) { return view ? m.color != ~0ull : material_solid(m); }
 
-void set_error(const std::string& msg);
+void set_error(const std::string& msg);  // svo_world.cpp (thread-local; read by svo_last_error)
+
+inline svo_block to_block(const Material& m) { return svo_block{m.flags, m.color, m.meta}; }
+
+// voxel coordinates wrap to the extent 4^levels (tetrahexa_tree.cpp:127-129 reads only these bits)
+inline uint32_t wrap_mask(int32_t levels) { return (1u << (2 * levels)) - 1u; }
+
+// ref + the mask bits below `slot` (svo_common.h Node): the node index of an INTERIOR node's child, the index in
+// mats of a non-uniform BRICK's voxel.  The slot's own bit must be set.
+inline uint32_t packed_index(const Node& n, uint32_t slot) { return n.ref + (uint32_t)__builtin_popcountll(n.mask & ((1ull << slot) - 1ull)); }
 
 // RGB_TO_U64 (src/types.hpp:6-9)
 inline uint64_t rgb_to_u64(int r, int g, int b) {
@@ -39,6 +49,12 @@ inline uint64_t rgb_to_u64(int r, int g, int b) {
 }
 
 }  // namespace svo
+
+#define SVO_FAIL(code, msg)     \
+    do {                        \
+        svo::set_error(msg);    \
+        return (code);          \
+    } while (0)
 
 // Linearised tree: host image + optional HBM copy
 struct svo_tree {
@@ -60,7 +76,7 @@ struct svo_tree {
     mutable int32_t ao_plan_n = 0, ao_plan_steps = -1;
     mutable std::mutex pick_mu;  // one pick ray at a time per tree (d_pick)
     uint64_t device_bytes = 0;
-    // incremental edits (svo_tree_update in svo_world.cpp, svo_tree_sync in svo_device.hip): changed
+    // incremental edits (svo_tree_update in svo_linearise.cpp, svo_tree_sync in svo_device.hip): changed
     // node blocks are appended; superseded ones are garbage until the next full rebuild
     uint64_t garbage_nodes = 0, garbage_mats = 0;
     uint64_t synced_nodes = 0, synced_mats = 0;  // prefix of nodes / mats already in HBM
@@ -117,8 +133,8 @@ namespace svo {
 constexpr size_t kSidePick = 0;     // svo_cast_ray_from_cam's result record (64 B)
 constexpr size_t kSideGuard = 256;  // u32: progress-guard trips of every launch over the tree (svo_tree_guard_trips)
 constexpr size_t kSideBytes = 4096;
-int32_t tree_top_y(const svo_tree* t);  // svo_world.cpp
-// Column ceilings (svo_world.cpp): per aligned block of 4^k x 4^k columns, k = kCeilK0 .. levels - 1 (at
+int32_t tree_top_y(const svo_tree* t);  // svo_tree.cpp
+// Column ceilings (svo_tree.cpp): per aligned block of 4^k x 4^k columns, k = kCeilK0 .. levels - 1 (at
 // most kCeilMax levels), the highest stored voxel row in those columns (-1: none) — every voxel above it
 // in the block is empty, whatever the tree holds (overhangs included).  Level j's blocks are row-major
 // [z][x] at out[off[j] ..]; returns the number of levels.

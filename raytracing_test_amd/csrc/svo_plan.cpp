@@ -1,5 +1,6 @@
 // svo_plan.cpp — the host arithmetic of svo_plan.h: the AO plan's simulation, a frame launch's octant, segment and
-// axis set-up, the ceiling pair / quad tables, what a sync has to move, and the frame schedule's decisions.
+// axis set-up, the ceiling pair / quad tables, what a sync has to move, the frame schedule's decisions, and a launch's
+// block and ray counts (svo_cast_blocks, svo_cast_count).
 #include "svo_plan.h"
 
 #include <math.h>
@@ -267,3 +268,47 @@ SchedPlan sched_decide(svo_tree::Sched& s, int64_t blocks, const int64_t sig[7],
 }
 
 }  // namespace svo
+
+// frames of a frame-mode desc (validated: 1 .. SVO_MAX_FRAMES, origins given for more than one)
+static int desc_frames(const svo_cast_desc* d, const char* fn, int32_t* nf) {
+    *nf = d->n_frames <= 1 ? 1 : d->n_frames;
+    if (d->n_frames < 0 || d->n_frames > SVO_MAX_FRAMES) SVO_FAIL(SVO_EINVAL, std::string(fn) + ": n_frames outside [0, SVO_MAX_FRAMES]");
+    if (d->n_frames > 1 && !d->frame_origins) SVO_FAIL(SVO_EINVAL, std::string(fn) + ": n_frames > 1 without frame_origins");
+    return SVO_OK;
+}
+
+extern "C" int svo_cast_blocks(const svo_cast_desc* d, int64_t* n) {
+    if (!d || !n) SVO_FAIL(SVO_EINVAL, "svo_cast_blocks: NULL argument");
+    if (d->ray_dirs) {
+        *n = d->n_rays > 0 ? ((int64_t)d->n_rays + 63) / 64 : 0;
+        return SVO_OK;
+    }
+    if (d->width <= 0 || d->height <= 0 || d->tile_row_step <= 0 || d->tile_row_start < 0)
+        SVO_FAIL(SVO_EINVAL, "svo_cast_blocks: bad frame geometry");
+    int32_t nf = 1;
+    int rc = desc_frames(d, "svo_cast_blocks", &nf);
+    if (rc) return rc;
+    const int32_t tile_rows = (d->height + 7) / 8;
+    const int64_t rows = d->tile_row_start < tile_rows ? (tile_rows - d->tile_row_start + d->tile_row_step - 1) / d->tile_row_step : 0;
+    const int32_t lh = svo::frame_wave_lh(d->flags), cols = svo::frame_wave_cols(d->width, lh);
+    *n = (rows + svo::frame_half_rows((int32_t)rows, d->flags, lh, cols, nf)) * cols * nf;
+    return SVO_OK;
+}
+
+extern "C" int svo_cast_count(const svo_cast_desc* d, int64_t* n) {
+    if (!d || !n) SVO_FAIL(SVO_EINVAL, "svo_cast_count: NULL argument");
+    if (d->ray_dirs) {
+        *n = d->n_rays;
+        return SVO_OK;
+    }
+    if (d->width <= 0 || d->height <= 0 || d->tile_row_step <= 0 || d->tile_row_start < 0)
+        SVO_FAIL(SVO_EINVAL, "svo_cast_count: bad frame geometry");
+    int32_t nf = 1;
+    int rc = desc_frames(d, "svo_cast_count", &nf);
+    if (rc) return rc;
+    const int32_t tile_rows = (d->height + 7) / 8;
+    int64_t rows = 0;
+    for (int32_t r = d->tile_row_start; r < tile_rows; r += d->tile_row_step) rows += std::min(8, d->height - r * 8);
+    *n = rows * d->width * nf;
+    return SVO_OK;
+}

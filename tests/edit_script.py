@@ -2,7 +2,7 @@
 (svo_tree_update: a solid tree and a VIEW_ALL scene tree each get their own update call per edit) and to the oracle's
 reference-layout tree: the fixture of tests/test_patched_host.py and tests/test_gpu_patched_trees.py.
 
-The edits are chosen for the shapes only a patched tree holds (svo_world.cpp, "Incremental edits"): an interior node
+The edits are chosen for the shapes only a patched tree holds (svo_linearise.cpp, "Incremental edits"): an interior node
 whose mask went to 0 under a set bit of its parent (a lone voxel deleted), 64 SOLID siblings of one material (a 16^3
 filled by 4^3 puts), child blocks rewritten at the tail of the node array, a record rewritten in place, ceilings that
 rise and fall, and, at 3 levels, a world that becomes empty, uniform and mixed again through edits of the root.

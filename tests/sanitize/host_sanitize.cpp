@@ -1,10 +1,10 @@
 // Host code of libsvo_rt under AddressSanitizer + UndefinedBehaviorSanitizer (SURVEY.md §5 "race detection /
 // sanitizers": on host code only — GPU sanitizers are not available on the pool).  Built and run by
-// tests/test_sanitizers.py from raytracing_test_amd/csrc/svo_world.cpp: world edits, every builder in
-// both views, incremental updates (patch, growth, rebuild), lookups, export and the checkpoint round trip;
-// and from svo_plan.cpp, the launch planning: the frame octant, the segment test, the ceiling tables kept up
-// to date over edits, the AO plan image, the sync bookkeeping, the frame schedule's decisions and the choice of the
-// cast kernel's instance.
+// tests/test_sanitizers.py from every host file of raytracing_test_amd/csrc (build.py HOST_SRCS): world edits, every
+// builder in both views, incremental updates (patch, growth, rebuild), lookups, export and the checkpoint round trip
+// (svo_world.cpp, svo_linearise.cpp, svo_terrain.cpp, svo_tree.cpp, svo_tree_file.cpp); and from svo_plan.cpp, the
+// launch planning: the frame octant, the segment test, the ceiling tables kept up to date over edits, the AO plan
+// image, the sync bookkeeping, the frame schedule's decisions and the choice of the cast kernel's instance.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>

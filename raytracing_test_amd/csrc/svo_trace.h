@@ -510,31 +510,36 @@ __device__ __forceinline__ uint32_t lookup(const CastParams& P, const Mem& mem, 
     // descend (one exit: no per-exit register copies)
     uint32_t res = R_EMPTY;
     if (SPLIT) {
-        bool pend = true;  // node ni - 1 occupies the cell and is not loaded yet
-        bool more = dd < P.levels - 1;
+        // Node ni - 1 occupies the cell and is not loaded yet.  Across the back-edge go ni, dd and one flag: dd counts
+        // only the levels whose child is pending (occupied, under an interior node), so a lane leaves the loop with
+        // dd == levels - 1 exactly when its brick-level node is pending (also a lane that starts there), and the
+        // other lanes' outcome is read after the loop from the last node they loaded (binfo; par.sh is its shift).
+        const int32_t dl = P.levels - 1;
+        bool more = dd < dl;
         while (more) {
             if (STATS) {
                 st.wv_descents += wave_lead();
                 st.loads++;
             }
             const Node n = mem.load(ni);
-            const uint32_t sh = (uint32_t)(2 * (P.levels - 1 - dd));
+            const uint32_t sh = (uint32_t)(2 * (dl - dd));
             path.put(dd, n.mask, n.ref);
             par.mask = n.mask;
             par.ref = n.ref;
             binfo = n.info;
             const uint64_t t = slot_top(n.mask, child_slot(w[0], w[1], w[2], sh));
-            const bool occ = (int64_t)t < 0;
             const bool solid = (n.info & K_KIND_MASK) == K_SOLID;
             par.sh = PSH && solid ? sh + 2u : sh;
             ni = popc_add(t, n.ref);
-            dd++;
-            pend = occ && !solid;
-            more = pend && dd < P.levels - 1;
-            sh_out = occ ? 0u : sh;
-            res = solid ? R_SOLID : R_EMPTY;
+            const bool pend = (int64_t)t < 0 && !solid;
+            dd += pend ? 1 : 0;
+            more = pend && dd < dl;
         }
-        if (pend) {  // the brick level: a BRICK or SOLID leaf
+        // ended above the bricks: a SOLID region, or an empty child cell of the last node (shift par.sh; sh_out is read
+        // for R_EMPTY only).  (Taken on every lane: the brick level's lanes overwrite it.)
+        sh_out = par.sh;
+        res = (binfo & K_KIND_MASK) == K_SOLID ? R_SOLID : R_EMPTY;
+        if (dd == dl) {  // the brick level: a BRICK or SOLID leaf
             if (STATS) {
                 st.wv_descents += wave_lead();
                 st.loads++;
@@ -1036,15 +1041,16 @@ __device__ __forceinline__ Hit trace(const CastParams& P, const Mem& mem, const 
             kind = lookup<LOOK>(P, mem, path, w, moved, par, sh, bmask, bref, binfo, st);
             jump = 0u;
         }
-        if (kind == R_SOLID) {
-            mat = binfo >> 16;
-            done = true;
-        } else if (kind == R_BRICK) {
-            if (STATS) st.bricks++;
-            pend = true;
-        } else if (R.steps <= 0) {
-            done = true;
-        } else if (!(fast && [&] {
+        // The lookup's outcome as lane predicates, taken once (an else-if chain here cost a lane-mask save, split and
+        // rejoin per arm): a SOLID region or a brick; else the cell is empty, and the ray's budget is spent, or it
+        // crosses the empty box in closed form (fast), or it steps through it voxel by voxel.  The budget is tested
+        // before the crossing changes it.
+        const bool k_solid = kind == R_SOLID, k_brick = kind == R_BRICK;
+        const bool open = !k_solid && !k_brick && R.steps > 0;  // an empty cell with budget left
+        const bool cross = open && fast;
+        bool crossed = false;
+        if (cross) {
+            crossed = [&] {
                        int32_t ex[3];
                        if (REFLECT) dir_flags(R.s, ud);  // reflections and refractions flip steps
                        // (a wave whose every crossing is a ceiling move — the air above the terrain — skips the forward
@@ -1069,21 +1075,26 @@ __device__ __forceinline__ Hit trace(const CastParams& P, const Mem& mem, const 
                            if (STATS) st.ceil_moves++;
                        }
                        return moved_ok;
-                   }())) {
-            if (STATS && fast) st.skip_out++;
-            if (fast) {
-                done = true;  // the budget ends inside this empty box: steps after the loop
-                // (ESCAPE: where a ray without a hit ends is not output — a miss whose budget ends in empty space skips them)
-                if (ESCAPE && top >= 0) escaped = true;
-            } else {
-                // not exact: voxel steps to the end of this (empty) 4^3 brick, then a lookup
-                pend = true;
-                bmask = 0ull;
+                   }();
+        }
+        // a crossing that did not move: the budget ends inside this empty box (its steps are taken after the loop)
+        const bool boxed = cross && !crossed;
+        // not exact: voxel steps to the end of this (empty) 4^3 brick, then a lookup
+        const bool walk = open && !fast;
+        mat = k_solid ? binfo >> 16 : mat;
+        done = (!k_brick && !open) || boxed;  // a SOLID region, a spent budget, or one that ends in this box
+        pend = k_brick || walk;
+        bmask = walk ? 0ull : bmask;
+        // (ESCAPE: where a ray without a hit ends is not output — a miss whose budget ends in empty space skips them)
+        if (ESCAPE && top >= 0) escaped = boxed;
+        if (STATS) {
+            if (k_brick) st.bricks++;
+            if (boxed) st.skip_out++;
+            if (crossed) {
+                st.skips++;
+                st.wv_skips += wave_lead();
+                st.skip_by_sh[min(3u, (sh >> 1) - 1u)]++;
             }
-        } else if (STATS) {
-            st.skips++;
-            st.wv_skips += wave_lead();
-            st.skip_by_sh[min(3u, (sh >> 1) - 1u)]++;
         }
         if (pend) {
             // voxel steps inside the brick, solid mask in registers.  (Postponing bricks until

@@ -46,6 +46,7 @@ CAST_NO_SCHEDULE = 65536  # keep the default dispatch order instead of the last 
 SCHED_MIN_BLOCKS = 4096  # frames of more blocks are scheduled (SVO_SCHED_MIN_BLOCKS)
 SCHED_PRIMARY, SCHED_AO, SCHED_SHADE = 0, 1, 2  # Tree.schedule kinds
 SCHED_GROUP = 4  # the schedule orders groups of this many consecutive blocks (SVO_SCHED_GROUP)
+# the slots of the counter buffer, in order: the mirror of the S_* enum of csrc/svo_stats.h (tests/test_host.py holds the two together)
 STAT_NAMES = ("rays", "lookups", "node_loads", "skips", "skip_budget_out", "brick_steps", "plain_steps", "lane_work",
               "wave_max_work_x64", "skips_4", "skips_16", "skips_64", "skips_256plus", "bricks",
               "wave_iters", "wave_brick_steps",

@@ -173,7 +173,7 @@ __global__ __launch_bounds__(kBlock, STATS ? 6 : (SHADE ? (DIRS != 0 ? kShadeWav
                 if (P.ao_plan && pfin.sh < 2u * (uint32_t)P.levels && (uint32_t)lx < (1u << 23) && (uint32_t)ly < (1u << 23) && (uint32_t)lz < (1u << 23)) {
                     uint32_t aol = 0u;
                     cnt = ao_count_plan(P, mem, path, pfin, h, l, ax, -st, aol);
-                    if (STATS) atomicAdd(P.stats + 22, (unsigned long long)aol);
+                    if (STATS) atomicAdd(P.stats + S_AO_NODE_LOADS, (unsigned long long)aol);
                 } else {
                     const float ao_o[3] = {(float)lx + 0.5f, (float)ly + 0.5f, (float)lz + 0.5f};
                     for (int32_t i = 0; i < P.ao_n; i++) {

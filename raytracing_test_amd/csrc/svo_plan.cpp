@@ -119,7 +119,7 @@ int frame_dirs(const RayGen& rg, int32_t width, int32_t height, int32_t flags) {
     return code;
 }
 
-// Can the launch hold rays that are not linear (svo_trace.h, "Exact closed-form skipping")?  From an
+// Can the launch hold rays that are not linear (svo_exact.h, "Exact closed-form skipping")?  From an
 // integral or half-integral origin every ray is (lin_origin, with budgets below 2^28 every sum it
 // takes is exact); explicit rays are not inspected.  The instance without segments relies on it
 // (trace: TRACK); SVO_CAST_SEGMENTS forces the other one (the same results).

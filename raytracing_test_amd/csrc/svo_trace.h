@@ -1,768 +1,20 @@
-// svo_trace.h — device code of one ray: the exact closed-form skipping, the region lookup, the brick walk, the
-// column-ceiling march and trace() itself (the semantics are in svo_cast_kernel.h's header note).
+// svo_trace.h — one ray: the trace<OPT> option word and trace() itself (the semantics are in svo_cast_kernel.h's header
+// note).  The one header svo_shade.h includes.  The rest of a ray's device code is in the eight headers below, one concern
+// each, included in the order of their definitions (the map of the traversal code):
 #pragma once
 
 #include <algorithm>
 
 #include "svo_cast_params.h"
 
-// ------------------------------------------------------------------------------------------------
-// Exact closed-form skipping.  castRayFromCam's axis choice (ray_caster.cpp:71-80) is, for non-NaN
-// values, the lexicographic minimum of (T_axis, rank) with rank z < y < x: x wins only when
-// strictly smallest, y beats z only when strictly smaller.  Each axis' crossings form the sequence
-// T, fl(T+a), fl(fl(T+a)+a), ... (deltaPos += absDelta in double).  absDelta is an f32 value
-// widened to f64: 24 significant bits, a multiple of 2^(ea-23).
-//  * Linear rays: when every partial sum a ray can reach (<= budget+2 terms) stays below
-//    2^(lsb+53) — lsb = lowest set bit of T and a — every sum is exact and T + k*a computed directly
-//    equals the k-fold accumulation bit for bit (e.g. always from integral camera positions).
-//  * Every other ray (budget < 2^20, finite values): |T| stays below 2^(ea+22), so a is a multiple
-//    of ulp(T) and every crossing below B = 2^(e+1) (e = the binade of |T|) is an exact,
-//    representable multiple of ulp(T); the first crossing at or above B is that exact sum rounded
-//    once, which fma(k, a, T) also computes.  Only later crossings (one more rounding per binade
-//    entered) drift from the closed form, so the crossings are exact segment by segment
-//    (seg_cap), and an empty region is crossed in a few moves (skip_box with seg).
-// A ray crosses an empty region in O(1): the first event to leave the region is the lexicographic
-// minimum of the three per-axis exit events, and the events before it on the other axes are
-// counted by division (with an exact fix-up).  Rays outside both domains step voxel by voxel
-// (still without memory traffic inside known-empty regions).  All paths give identical results
-// (tests).
-// ------------------------------------------------------------------------------------------------
-// lowest set bit (power of two) of |x|: x finite and nonzero; denormals -> 1 << 20 ("not fast")
-__device__ __forceinline__ int dbl_lsb(uint32_t hi, uint32_t lo) {
-    const int e = (int)((hi >> 20) & 0x7FFu);
-    const uint32_t mh = (hi & 0xFFFFFu) | 0x100000u;  // hidden bit
-    const int tz = lo ? (int)__builtin_ctz(lo) : 32 + (int)__builtin_ctz(mh);
-    return e == 0 ? (1 << 20) : e - 1075 + tz;
-}
-
-// a: positive, normal, finite; T: finite (the closed forms' domain)
-__device__ __forceinline__ bool axis_ok(double T, double a) {
-    const uint32_t th = (uint32_t)((uint64_t)__double_as_longlong(T) >> 32) & 0x7FFFFFFFu;
-    const uint32_t ah = (uint32_t)((uint64_t)__double_as_longlong(a) >> 32);
-    const uint32_t et = th >> 20, ea = (ah >> 20) & 0x7FFu;
-    return ((unsigned)((ah >> 31) == 0u) & (unsigned)(ea - 1u < 0x7FEu) & (unsigned)(et != 0x7FFu)) != 0u;  // (branch-free)
-}
-
-// every partial sum exact ("linear" axis: no rounding at all); axis_ok(T, a) holds
-__device__ __forceinline__ bool exact_axis(double T, double a, int32_t budget) {
-    const uint32_t th = (uint32_t)((uint64_t)__double_as_longlong(T) >> 32) & 0x7FFFFFFFu, tl = (uint32_t)__double_as_longlong(T);
-    const uint32_t ah = (uint32_t)((uint64_t)__double_as_longlong(a) >> 32), al = (uint32_t)__double_as_longlong(a);
-    const int u = (th | tl) ? min(dbl_lsb(th, tl), dbl_lsb(ah, al)) : dbl_lsb(ah, al);
-    const double bound = __builtin_fabs(T) + (double)(budget + 2) * a;
-    const int eb = (int)((uint32_t)((uint64_t)__double_as_longlong(bound) >> 52) & 0x7FFu) - 1023;
-    return eb + 1 <= u + 52;  // bound < 2^(u+52): the unrounded bound < 2^(u+53)
-}
-
-struct Ray {
-    int32_t r[3];   // current voxel (unwrapped)
-    double T[3];    // next crossing per axis (deltaPos)
-    float af[3];    // absDelta: an f32 value widened to f64 by the reference (ray_caster.cpp:35-41)
-    int32_t s[3];   // step
-    int32_t steps;  // budget left
-    uint32_t axis;  // axis of the last step (3: none)
-    double tlast;   // crossing value of the last step (converted to the f32 output once, at the end)
-    float ia[3];    // f32 estimate of 1/absDelta (crossing counts only estimate with it)
-    int32_t rb[3];  // segment-cached instances (skip_box RB): the cell of each axis' last exact crossing
-    __device__ __forceinline__ float inv_a(int k) const { return ia[k]; }
-    __device__ __forceinline__ double a(int k) const { return (double)af[k]; }
-};
-
-// T + k*a for a fast ray: exact (exact_axis), so one fused operation gives the same double
-__device__ __forceinline__ double on_grid(double T, int32_t k, double a) {
-    return __builtin_fma((double)k, a, T);
-}
-
-// The f32 count estimates (count_est) need every exit event V in f32 range: V is at most the
-// smallest absDelta times budget + 2 (< 2^21), so a ray whose every absDelta is 2^100 or more (a
-// direction vector with every component below 2^-100) takes the stepping path.  (Frame rays have unit
-// directions: their smallest absDelta is at most sqrt(3).)
-__device__ __forceinline__ bool span_ok(const Ray& R) {
-    return __builtin_fminf(__builtin_fminf(R.af[0], R.af[1]), R.af[2]) < 0x1p100f;
-}
-
-// one DDA step (ray_caster.cpp:70-80), branch-free
-__device__ __forceinline__ void dda_step(Ray& R) {
-    const bool cx = (R.T[0] < R.T[1]) && (R.T[0] < R.T[2]);
-    const bool cy = !cx && (R.T[1] < R.T[2]);
-    const bool cz = !cx && !cy;
-    R.tlast = cx ? R.T[0] : (cy ? R.T[1] : R.T[2]);
-    R.axis = cx ? 0u : (cy ? 1u : 2u);
-    R.r[0] += cx ? R.s[0] : 0;
-    R.r[1] += cy ? R.s[1] : 0;
-    R.r[2] += cz ? R.s[2] : 0;
-    R.T[0] = cx ? R.T[0] + R.a(0) : R.T[0];
-    R.T[1] = cy ? R.T[1] + R.a(1) : R.T[1];
-    R.T[2] = cz ? R.T[2] + R.a(2) : R.T[2];
-    R.steps--;
-}
-
-// Wave-uniform step directions per axis: 1 = every active lane steps +, 2 = every one steps -,
-// 0 = mixed.  Lanes only retire while a ray runs, so flags taken at its start stay true.
-__device__ __forceinline__ void dir_flags(const int32_t s[3], uint32_t ud[3]) {
-    const uint64_t ex = __builtin_amdgcn_read_exec();
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const uint64_t b = __ballot(s[k] > 0);
-        ud[k] = b == ex ? 1u : (b == 0ull ? 2u : 0u);
-    }
-}
-
-// r + n or r - n by the step sign s; ud: wave-uniform sign (dir_flags) or 0
-__device__ __forceinline__ int32_t step_by(int32_t r, int32_t n, int32_t s, uint32_t ud) {
-    if (ud == 1u) return r + n;
-    if (ud == 2u) return r - n;
-    return s > 0 ? r + n : r - n;  // (s * n as a 24-bit multiply-add became v_mad_u64_u32)
-}
-
-// A run of free cells through a 4-cell line (occupancy bits 0-3; higher bits are ignored) from the
-// ray's cell c (free itself) in its step direction: t = cells in the run (>= 1), m = their slots.
-// A sentinel bit stands for the end of the line: one ctz (up) or one clz (down) finds the run.
-// ((1 << w) - 1) << o in one v_bfm_b32 (clang emits a shift, a not and a shift)
-__device__ __forceinline__ uint32_t bfm(uint32_t w, uint32_t o) {
-    uint32_t r;
-    asm("v_bfm_b32 %0, %1, %2" : "=v"(r) : "v"(w), "v"(o));
-    return r;
-}
-__device__ __forceinline__ void run_up(uint32_t occ, uint32_t c, uint32_t& t, uint32_t& m) {
-    t = (uint32_t)__builtin_ctz((occ | 16u) >> c);
-    m = bfm(t, c);
-}
-__device__ __forceinline__ void run_down(uint32_t occ, uint32_t c, uint32_t& t, uint32_t& m) {
-    // slots below c at bits 1..c, the sentinel at bit 0: the highest set bit is the run's first slot
-    const uint32_t lo = 31u - (uint32_t)__builtin_clz(__builtin_amdgcn_ubfe((occ << 1) | 1u, 0u, c + 1u));
-    t = c + 1u - lo;
-    m = bfm(t, lo);
-}
-__device__ __forceinline__ void run_fwd(uint32_t occ, uint32_t c, bool pos, uint32_t ud, uint32_t& t, uint32_t& m) {
-    if (ud == 1u) {
-        run_up(occ, c, t, m);
-    } else if (ud == 2u) {
-        run_down(occ, c, t, m);
-    } else {
-        uint32_t t0, m0, t1, m1;
-        run_up(occ, c, t0, m0);
-        run_down(occ, c, t1, m1);
-        t = pos ? t0 : t1;
-        m = pos ? m0 : m1;
-    }
-}
-
-// per 16-bit half of v: 1 if it is nonzero — one packed min (clang scalarises the vector form)
-__device__ __forceinline__ uint32_t nonzero16(uint32_t v) {
-    uint32_t r;
-    asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(v), "s"(0x00010001u));
-    return r;
-}
-
-// Grow the ray's empty child slot into a forward box of empty sibling slots (greedy: the run along x
-// from the mask row, then whole rows along z; one cell in y), all from the parent's 64-bit child
-// mask in registers, without loops.  Returns per-axis steps to leave it, less one (the index of the
-// step that leaves).
-__device__ __forceinline__ void box_exits(const uint32_t w[3], const int32_t s[3], uint32_t sh, uint64_t pmask, const uint32_t ud[3],
-                                          int32_t e[3]) {
-    const uint32_t cx = __builtin_amdgcn_ubfe(w[0], sh, 2u), cy = __builtin_amdgcn_ubfe(w[1], sh, 2u), cz = __builtin_amdgcn_ubfe(w[2], sh, 2u);
-    const bool px = s[0] > 0, py = s[1] > 0, pz = s[2] > 0;
-    const uint32_t lo = (uint32_t)pmask, hi = (uint32_t)(pmask >> 32);
-    uint32_t tx, xm, tz, zm;
-    // x run through the row (cy, cz)
-    run_fwd((uint32_t)(pmask >> (16u * cz + 4u * cy)), cx, px, ud[0], tx, xm);
-    // rows (cy, z) over the x run: bit z (bits 0, 16 -> 0, 1 of the low half, 2, 3 of the high) =
-    // the row holds a solid slot
-    const uint32_t xs = xm << (4u * cy);
-    const uint32_t xl = xs | (xs << 16);
-    const uint32_t zc = nonzero16(lo & xl) | (nonzero16(hi & xl) << 2);
-    run_fwd(zc | (zc >> 15), cz, pz, ud[2], tz, zm);
-    (void)zm;
-    // (growing the box along y as well — whole planes over the x run x z run — cost more per crossing
-    // than it saved in crossings: without it C3 2.7 %, C5 3.7 %, C2 0.5-2.7 % faster; x runs alone
-    // were 16 % slower at C3 / C5)
-    const uint32_t ty = 1u;
-    // steps to leave: t cells of 2^sh voxels, less the part of the current cell behind the ray;
-    // less one: x + ~y = x - y - 1
-    const uint32_t m = (1u << sh) - 1u;
-    e[0] = (int32_t)((tx << sh) + ~((px ? w[0] : ~w[0]) & m));
-    e[1] = (int32_t)((ty << sh) + ~((py ? w[1] : ~w[1]) & m));
-    e[2] = (int32_t)((tz << sh) + ~((pz ? w[2] : ~w[2]) & m));
-}
-
-// The child mask shifted so that slot sl's bit lands on bit 63 (m << (63 - sl)): its sign is the
-// occupancy, and one more shift leaves exactly the lower slots' bits, whose popcount is the
-// child's rank among its siblings.
-__device__ __forceinline__ uint64_t slot_top(uint64_t m, uint32_t sl) { return m << (sl ^ 63u); }
-// popcount(x) + acc through the accumulating v_bcnt_u32_b32 (clang adds acc separately)
-__device__ __forceinline__ uint32_t popc_add(uint64_t x, uint32_t acc) {
-    uint32_t r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"((uint32_t)x), "v"(acc));
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"((uint32_t)(x >> 32)), "v"(r));
-    return r;
-}
-
-// #{ j >= 0 : T + j*a < V } or #{ j >= 0 : T + j*a <= V } = m + [E < V] or m + [E <= V] with
-// E = T + m*a and the estimate m = floor((V-T)/a + 1/2) (for <=, the count is floor(x) + 1 with
-// x = (V-T)/a, and m is that or one less)
-// per-lane selects and a carry-in add on a wave mask held in SGPRs
-__device__ __forceinline__ uint32_t sel32(uint64_t m, uint32_t a, uint32_t b) {
-    uint32_t r;
-    asm("v_cndmask_b32_e64 %0, %2, %1, %3" : "=v"(r) : "v"(a), "v"(b), "s"(m));
-    return r;
-}
-__device__ __forceinline__ double sel64(uint64_t m, double a, double b) {
-    const uint64_t ua = (uint64_t)__double_as_longlong(a), ub = (uint64_t)__double_as_longlong(b);
-    const uint32_t lo = sel32(m, (uint32_t)ua, (uint32_t)ub), hi = sel32(m, (uint32_t)(ua >> 32), (uint32_t)(ub >> 32));
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-__device__ __forceinline__ int32_t add_bit(int32_t x, uint64_t m) {
-    int32_t r;
-    uint64_t co;
-    asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(r), "=s"(co) : "v"(x), "s"(m));
-    return r;
-}
-// The difference V - T is taken in f32 from f32 copies of both (one conversion of V serves the three
-// axes; V < 2^121 by span_ok, so its copy is finite, and a T beyond the f32 range only makes the
-// estimate 0, its count): T / a and V / a stay below budget + 2 < 2^20 + 2 (V is at most T + steps * a on every axis),
-// so the two conversions, the subtraction, the 1-ulp reciprocal and the fma move the estimate by less
-// than 6 * 2^20 * 2^-24 = 3/8 < 1/2 — m stays c - 1 or c
-// V, or nextup(V) on the lanes of m (V >= 0 and finite: the bits plus one)
-__device__ __forceinline__ double next_if(double V, uint64_t m) {
-    const uint64_t b = (uint64_t)__double_as_longlong(V);
-    uint32_t lo, hi;
-    uint64_t c, c2;
-    asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(lo), "=s"(c) : "v"((uint32_t)b), "s"(m));
-    asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(hi), "=s"(c2) : "v"((uint32_t)(b >> 32)), "s"(c));
-    (void)c2;
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-__device__ __forceinline__ int32_t count_est(double T, double a, float inva, double V, float Vf, double& E) {
-    uint32_t mu;
-    asm("v_cvt_u32_f32 %0, %1" : "=v"(mu) : "v"(__builtin_fmaf(Vf - (float)T, inva, 0.5f)));
-    E = on_grid(T, (int32_t)mu, a);
-    return (int32_t)mu;
-}
-
-// Exact segments.  From any state (T, a), the crossings T + i*a are multiples of 2^v, v = the lower
-// of the lowest set bits of T and a, so every crossing below B = 2^(v+53) is exact and representable,
-// and the first one at or above B is that sum rounded once, as fma(i, a, T) computes it too.  B is at
-// least 2^(e+1) (e = the binade of |T|: T is a multiple of ulp(T), and a of 2^(ea-23) > ulp(T) as
-// |T| < 2^(ea+22)); for a ray from a non-integral origin it is typically hundreds of crossings away,
-// and past it each binade the crossings enter costs one rounding.  seg_cap returns an index of a
-// crossing below B (at most the last one): the crossings 0 .. seg_cap + 1 are fma-exact.
-// lowest set bit exponent of |T| (zero: none, 2^20; subnormal: -1074, a safe underestimate)
-__device__ __forceinline__ int32_t lsb_exp(double T) {
-    const uint64_t b = (uint64_t)__double_as_longlong(T);
-    const uint32_t lo = (uint32_t)b, hi = (uint32_t)(b >> 32);
-    const int32_t e = (int32_t)((hi >> 20) & 0x7FFu);
-    const int32_t tz = lo ? (int32_t)__builtin_ctz(lo) : 32 + (int32_t)__builtin_ctz((hi & 0xFFFFFu) | 0x100000u);
-    return e != 0 ? e - 1075 + tz : ((b << 1) == 0ull ? (1 << 20) : -1074);
-}
-// A ray is linear, by a cheap sufficient test on its origin, when every coordinate is integral or
-// half-integral: dda_axis then starts at T = a, 0, a/2, 3a/2 or -a/2 (a multiple of half of a's
-// lowest set bit, 2^(la-1)), and with a budget below 2^20 every sum stays below 2^(la-1+53) — the
-// camera positions of integral poses, and the cell centres shadow and AO rays start from.
-__device__ __forceinline__ bool lin_origin(float o) {
-    const float o2 = o + o;
-    return o2 == __builtin_truncf(o2) && __builtin_fabsf(o) < 1073741824.0f;
-}
-
-// x = (B - T)/a is estimated as x~ within 2^-22 relative (f32 roundings, the 1-ulp reciprocal), so
-// floor(x~ * (1 - 2^-20)) < x: at most the count of crossings below B, less one (almost always equal)
-__device__ __forceinline__ int32_t seg_cap(double T, float af, float inva) {
-    const uint32_t ab = __float_as_uint(af);
-    const int32_t la = (int32_t)((ab >> 23) & 0xFFu) - 150 + (int32_t)__builtin_ctz(ab | 0x800000u);  // a: normal
-    const int32_t be = min(max(min(lsb_exp(T), la) + 53 + 1023, 1), 0x7FF);  // biased exponent of B (0x7FF: inf)
-    const double B = __longlong_as_double((long long)((uint64_t)(uint32_t)(be << 20) << 32));
-    uint32_t c;
-    asm("v_cvt_u32_f32 %0, %1" : "=v"(c) : "v"((float)(B - T) * inva * 0.99999905f));  // saturates (inf: 2^32 - 1)
-    return (int32_t)min(c, 1u << 30);  // (never negative: every skip takes at least its exit step)
-}
-
-// Cross an empty box, branch-free over the exit axis: ex[k] = steps along axis k that leave the box,
-// less one.  Returns false (state unchanged) when the budget ends inside the box.  seg (wave-uniform:
-// the wave holds rays that are not linear): each axis' exit event is also held to its exact segment (seg_cap); an exit on such a
-// bound is a virtual one inside the box (the next lookup finds the same empty cell in the parent's
-// mask, without a load, and the crossing continues).
-// RB: segment bounds cached as cells (R.rb): crossing i of axis k from the current state is the one
-// into cell r + s*i, so the bound seg_cap gave at some earlier state stays s*(rb - r) crossings ahead
-// while the ray has not passed it (every sum up to there is exact, from any state on the way); a
-// negative count means it has, and seg_cap is taken again from the current state
-template <bool TRACK = true, bool RB = false>
-__device__ __forceinline__ bool skip_box(Ray& R, const int32_t ex[3], bool seg) {
-    // exits beyond the budget are clamped (safe: total > steps)
-    int32_t e[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) e[k] = min(ex[k], R.steps);
-    if (seg && RB) {  // wave-uniform
-        int32_t cap[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++)  // (wrapping differences: |cap| < 2^31)
-            cap[k] = (int32_t)(R.s[k] > 0 ? (uint32_t)R.rb[k] - (uint32_t)R.r[k] : (uint32_t)R.r[k] - (uint32_t)R.rb[k]);
-        if (__ballot(min(min(cap[0], cap[1]), cap[2]) < 0) != 0ull) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                if (cap[k] < 0) {
-                    cap[k] = seg_cap(R.T[k], R.af[k], R.inv_a(k));
-                    R.rb[k] = (int32_t)(R.s[k] > 0 ? (uint32_t)R.r[k] + (uint32_t)cap[k] : (uint32_t)R.r[k] - (uint32_t)cap[k]);
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 3; k++) e[k] = min(e[k], cap[k]);
-    } else if (seg) {  // wave-uniform
-#pragma unroll
-        for (int k = 0; k < 3; k++) e[k] = min(e[k], seg_cap(R.T[k], R.af[k], R.inv_a(k)));
-    }
-    double E[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) E[k] = on_grid(R.T[k], e[k], R.a(k));
-    // lexicographic minimum of (E, rank) with rank z < y < x (the DDA rule applied to exits)
-    // exit flags as lane masks (SGPRs): selects and tie terms read them directly
-    // (ballots of single compares are the compare masks themselves)
-    const uint64_t mx = __ballot(E[0] < E[1]) & __ballot(E[0] < E[2]);
-    const uint64_t my = __ballot(E[1] < E[2]) & ~mx;
-    const double V = sel64(mx, E[0], sel64(my, E[1], E[2]));
-    // Events of another axis k that precede the exit event: T + j*a < V when k loses ties
-    // (rank_k > rank_b, i.e. k < b), else T + j*a <= V, which on doubles is < nextup(V).
-    // strict: x only when the exit is on y or z, y only when it is on z, z never.  On the exit
-    // axis b, E = V exactly (V is its e_b-th crossing, m = e_b): there the tie term is the flag b_b
-    // itself, so x and y need no second compare of their own for it.
-    int32_t n[3];
-    double F[3];
-    const float Vf = (float)V;
-    n[0] = count_est(R.T[0], R.a(0), R.inv_a(0), V, Vf, F[0]);
-    n[1] = count_est(R.T[1], R.a(1), R.inv_a(1), V, Vf, F[1]);
-    n[2] = count_est(R.T[2], R.a(2), R.inv_a(2), V, Vf, F[2]);
-    // (the terms of one axis are disjoint: a tie term implies F = V)
-    n[0] = add_bit(n[0], __ballot(F[0] < V) | mx);
-    // y's tie term: exit on x counts y's events <= V, i.e. < nextup(V) (V >= 0 finite: its bits + 1),
-    // taken by one integer add with the carry-in on mx instead of a second f64 compare
-    n[1] = add_bit(n[1], __ballot(F[1] < next_if(V, mx)) | my);
-    n[2] = add_bit(n[2], __ballot(F[2] <= V));
-    const int32_t total = n[0] + n[1] + n[2];
-    if (total > R.steps) return false;  // (a wrong count cannot hang the launch either: trace's progress guard)
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        R.T[k] = on_grid(R.T[k], n[k], R.a(k));
-        // a compile-time step (sign octant instances) adds or subtracts; else a 24-bit multiply-add
-        // (full rate; s = +-1, |n| < 2^21)
-        R.r[k] += __builtin_constant_p(R.s[k]) ? (R.s[k] > 0 ? n[k] : -n[k]) : __mul24(R.s[k], n[k]);
-    }
-    if (TRACK) R.tlast = V;  // (else recovered at the end of the ray: trace)
-    R.axis = sel32(mx, 0u, sel32(my, 1u, 2u));
-    R.steps -= total;
-    return true;
-}
-
-struct Stats {
-    uint32_t lookups, loads, skips, skip_out, brick_steps, plain_steps;
-    uint32_t skip_by_sh[4];  // crossings whose box is made of 2^sh cells: sh = 2, 4, 6, >= 8
-    uint32_t bricks;         // brick visits
-    uint32_t wv_iters, wv_brick;  // wave-level executions (counted on the first active lane): outer
-                                  // loop iterations, brick voxel steps
-    uint32_t root_starts, cache_empty;  // lookups started at the root; lookups answered by the
-                                        // parent mask
-    uint32_t path_starts;                          // lookups restarted from the LDS path
-    uint32_t wv_skips, wv_descents;                // wave-level crossings, descent levels
-    uint32_t no_progress;                          // loop iterations that consumed no budget (the guard's trips: 0)
-    uint32_t ceil_moves;                           // crossings of a column-ceiling box (no lookup)
-    uint32_t iters;                                // this lane's traversal iterations
-    uint32_t above_top;                            // iterations that start above the tree's highest stored row
-    uint32_t bends;                                // reflections and refractions (shading)
-    uint32_t tints, tint_iters;                    // refractive voxels passed; iterations that ended passing one
-};
-
-// true on one lane of the active lanes (wave-level counters)
-__device__ __forceinline__ bool wave_lead() {
-    return (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(__builtin_amdgcn_read_exec());
-}
-
-// wave-wide max / sum (diagnostics only)
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
-
-// Region lookup of a wrapped voxel: SOLID hit, an empty child cell (returns its shift), or the
-// brick holding the voxel (mask / ref / info returned).  tetrahexa_tree.cpp:124-152 on the
-// breadth-first layout.
-enum : uint32_t { R_EMPTY = 0u, R_BRICK = 1u, R_SOLID = 2u, R_CEIL = 3u };
-// Hit.info of a shading ray that left the loop early (ESCAPE): a miss whose remaining steps are all in empty voxels
-// (never written to a hit record: escaping is off when records are requested)
-constexpr uint32_t ESC_BIT = 1u << 19;
-
-// The interior node whose child region holds the ray's current cell, kept in registers: a move to
-// a sibling region reads the cached child mask (no load when the sibling is empty) and restarts
-// the descent at most one level down; leaving the parent's region restarts at the root, whose top
-// levels are staged in LDS.
-// per-lane path of the last descent in LDS
-struct Path {
-    // [depth][mask low, mask high, first child][lane] dwords: one address per depth (the three
-    // words at +0, +256, +512 bytes: ds_write2st64 / ds_read2st64 and one more)
-    uint32_t* __restrict__ w;
-    __device__ __forceinline__ void put(int32_t d, uint64_t mask, uint32_t ref) const {
-        uint32_t* e = w + d * (3 * kBlock);
-        e[0] = (uint32_t)mask;
-        e[kBlock] = (uint32_t)(mask >> 32);
-        e[2 * kBlock] = ref;
-    }
-    __device__ __forceinline__ uint64_t mask(int32_t d) const {
-        const uint32_t* e = w + d * (3 * kBlock);
-        return (uint64_t)e[0] | ((uint64_t)e[kBlock] << 32);
-    }
-    __device__ __forceinline__ uint32_t ref(int32_t d) const { return w[d * (3 * kBlock) + 2 * kBlock]; }
-};
-
-struct Parent {
-    uint64_t mask;
-    uint32_t ref;
-    uint32_t sh;  // child shift: a child region is 2^sh voxels wide, the parent's 2^(sh+2)
-};
-
-// Node reads.  Trees of up to kNarrowNodes nodes (4 GiB) read through a buffer resource with 32-bit
-// byte offsets (one shift per load, and buffer loads are never merged with the LDS path); larger
-// trees — the builders accept up to 2^32 nodes, 64 GiB — through 64-bit global addresses.  The host
-// picks the instance per tree (svo_cast.hip: node_addressing), so no index can wrap or fall outside
-// the resource and read zeros (an empty node) silently.
-// Loads take "one past" indices: ni1 = node index + 1 = first child + rank + 1, which is the popcount
-// of the child mask shifted so the child's own bit stays in (slot_top: no further shift), and the
-// bases sit one node before the array.
-constexpr uint64_t kNarrowNodes = 1ull << 28;  // below it, ni1 << 4 stays below 2^32
-
-struct BufNodes {
-    __amdgpu_buffer_rsrc_t rsrc;
-    const Node* __restrict__ base;
-    __device__ __forceinline__ explicit BufNodes(const Node* p)
-        : rsrc(__builtin_amdgcn_make_buffer_rsrc(const_cast<Node*>(p - 1), (short)0, (int)0xFFFFFFFFu, (int)0x00020000)), base(p) {}
-    __device__ __forceinline__ Node root() const { return base[0]; }  // (uniform: a scalar load)
-    __device__ __forceinline__ Node load(uint32_t ni) const {  // node ni - 1
-        const uint32_t off = ni << 4;
-        Node n;
-        n.mask = ((uint64_t)(uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0)) |
-                 ((uint64_t)(uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, off + 4, 0, 0) << 32);
-        n.ref = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, off + 8, 0, 0);
-        n.info = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, off + 12, 0, 0);
-        return n;
-    }
-};
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-struct WideNodes {
-    const __attribute__((address_space(1))) u32x4* p;
-    const Node* __restrict__ base;
-    __device__ __forceinline__ explicit WideNodes(const Node* q) : p((const __attribute__((address_space(1))) u32x4*)(q - 1)), base(q) {}
-    __device__ __forceinline__ Node root() const { return base[0]; }  // (uniform: a scalar load)
-    __device__ __forceinline__ Node load(uint32_t ni) const {  // node ni - 1
-        const u32x4 v = p[ni];  // 64-bit address: base + (u64)ni * 16
-        Node n;
-        n.mask = (uint64_t)v.x | ((uint64_t)v.y << 32);
-        n.ref = v.z;
-        n.info = v.w;
-        return n;
-    }
-};
-
-// lookup()'s compile-time options, one word (lookup<OPT>)
-enum : uint32_t {
-    L_STATS = 1u << 0,  // count into st (diagnostics)
-    // the levels above the bricks hold interior nodes or SOLID regions only; a SOLID region ends the ray, so the parent
-    // may be overwritten by it, and those levels need no leaf branch and no copies of the loaded node (the shading
-    // pass, whose callers read the final parent's regions, keeps the general loop)
-    L_SPLIT = 1u << 1,
-    // (AO instances: ao_count_plan reads the final parent's shift only) a SOLID region above the bricks leaves the shift
-    // of its own parent, so no path entry at or below the SOLID node is read back
-    L_PSH = 1u << 2,
-};
-template <uint32_t OPT, class Mem>
-__device__ __forceinline__ uint32_t lookup(const CastParams& P, const Mem& mem, const Path& path,
-                                           const uint32_t w[3], uint32_t moved, Parent& par, uint32_t& sh_out, uint64_t& bmask,
-                                           uint32_t& bref, uint32_t& binfo, Stats& st) {
-    static_assert((OPT & ~(L_STATS | L_SPLIT | L_PSH)) == 0u, "lookup: unknown option");
-    constexpr bool STATS = (OPT & L_STATS) != 0u, SPLIT = (OPT & L_SPLIT) != 0u, PSH = (OPT & L_PSH) != 0u;
-    uint32_t ni = 0u;
-    int32_t dd = 0;
-    if (STATS) st.lookups++;
-    {
-        // the previous voxel lies in the parent's region (every move starts inside it), so the
-        // bits in which the last step changed the stepped coordinate tell whether the ray left it
-        const uint32_t diff = moved;
-        if (diff >= (4u << par.sh)) {  // a bit at or above the parent region's size changed
-            // left the parent's region: the deepest node of the last descent whose region also
-            // holds this cell (depth levels-1-floor(h/2), h = highest differing bit) becomes the
-            // parent, read back from the per-lane path in LDS
-            const int32_t da = P.levels - 1 - (int32_t)((31u - (uint32_t)__builtin_clz(diff)) >> 1);  // (diff != 0)
-            par.mask = path.mask(da);
-            par.ref = path.ref(da);
-            par.sh = (uint32_t)(2 * (P.levels - 1 - da));
-            if (STATS) st.path_starts++;
-        }
-        sh_out = par.sh;
-        const uint64_t t = slot_top(par.mask, child_slot(w[0], w[1], w[2], par.sh));
-        if ((int64_t)t >= 0) {
-            if (STATS) st.cache_empty++;
-            return R_EMPTY;
-        }
-        ni = popc_add(t, par.ref);  // (one past: BufNodes)
-        dd = P.levels - (int32_t)(par.sh >> 1);  // depth of that child
-        if (STATS && dd == 0) st.root_starts++;
-    }
-    // descend (one exit: no per-exit register copies)
-    uint32_t res = R_EMPTY;
-    if (SPLIT) {
-        // Node ni - 1 occupies the cell and is not loaded yet.  Across the back-edge go ni, dd and one flag: dd counts
-        // only the levels whose child is pending (occupied, under an interior node), so a lane leaves the loop with
-        // dd == levels - 1 exactly when its brick-level node is pending (also a lane that starts there), and the
-        // other lanes' outcome is read after the loop from the last node they loaded (binfo; par.sh is its shift).
-        const int32_t dl = P.levels - 1;
-        bool more = dd < dl;
-        while (more) {
-            if (STATS) {
-                st.wv_descents += wave_lead();
-                st.loads++;
-            }
-            const Node n = mem.load(ni);
-            const uint32_t sh = (uint32_t)(2 * (dl - dd));
-            path.put(dd, n.mask, n.ref);
-            par.mask = n.mask;
-            par.ref = n.ref;
-            binfo = n.info;
-            const uint64_t t = slot_top(n.mask, child_slot(w[0], w[1], w[2], sh));
-            const bool solid = (n.info & K_KIND_MASK) == K_SOLID;
-            par.sh = PSH && solid ? sh + 2u : sh;
-            ni = popc_add(t, n.ref);
-            const bool pend = (int64_t)t < 0 && !solid;
-            dd += pend ? 1 : 0;
-            more = pend && dd < dl;
-        }
-        // ended above the bricks: a SOLID region, or an empty child cell of the last node (shift par.sh; sh_out is read
-        // for R_EMPTY only).  (Taken on every lane: the brick level's lanes overwrite it.)
-        sh_out = par.sh;
-        res = (binfo & K_KIND_MASK) == K_SOLID ? R_SOLID : R_EMPTY;
-        if (dd == dl) {  // the brick level: a BRICK or SOLID leaf
-            if (STATS) {
-                st.wv_descents += wave_lead();
-                st.loads++;
-            }
-            const Node n = mem.load(ni);
-            bmask = n.mask;
-            bref = n.ref;
-            binfo = n.info;
-            sh_out = 2u;
-            res = (n.info & K_KIND_MASK) == K_SOLID ? R_SOLID : R_BRICK;
-        }
-        return res;
-    }
-    bool more = dd < P.levels;
-    while (more) {
-        if (STATS) {
-            st.wv_descents += wave_lead();
-            st.loads++;
-        }
-        const Node n = mem.load(ni);
-        const uint32_t kind = n.info & K_KIND_MASK;
-        // (read only for BRICK / SOLID results: written on every load, so the previous values need
-        // no copies around it)
-        bmask = n.mask;
-        bref = n.ref;
-        binfo = n.info;
-        if (kind == K_INTERIOR) {
-            const uint32_t sh = (uint32_t)(2 * (P.levels - 1 - dd));
-            path.put(dd, n.mask, n.ref);
-            par.mask = n.mask;
-            par.ref = n.ref;
-            par.sh = sh;
-            const uint64_t t = slot_top(n.mask, child_slot(w[0], w[1], w[2], sh));
-            const bool occ = (int64_t)t < 0;
-            ni = popc_add(t, n.ref);
-            dd++;
-            more = occ && dd < P.levels;
-            sh_out = occ ? 0u : sh;  // (occupied at the last level only in a malformed tree: one voxel)
-        } else {
-            sh_out = 2u;
-            res = kind == K_SOLID ? R_SOLID : R_BRICK;
-            more = false;
-        }
-    }
-    return res;
-}
-
-__device__ __forceinline__ uint32_t brick_material(const uint16_t* mats, uint64_t mask, uint32_t ref, uint32_t info, uint32_t v) {
-    return (info & K_UNIFORM) ? (info >> 16) : (uint32_t)mats[ref + (uint32_t)__popcll(mask & ((1ull << v) - 1ull))];
-}
-
-__device__ __forceinline__ void wrap3(const Ray& R, uint32_t wm, uint32_t w[3]) {
-    w[0] = (uint32_t)R.r[0] & wm;
-    w[1] = (uint32_t)R.r[1] & wm;
-    w[2] = (uint32_t)R.r[2] & wm;
-}
-
-// Voxel steps through a brick on its register mask (see trace): returns the voxel index reached;
-// `left` = per-axis steps left in the brick (bytes 0-2, a zero byte = left the brick), `solid` =
-// stopped on a solid voxel.  The crossing value of every step is kept (recovering it after the
-// walk as T - a, exact for fast rays, measured no faster).
-// TRACK: keep the crossing value of every step (R.tlast); without it trace recovers the last one
-// once, at the end of the ray (exact sums: T - a).  (A wave-uniform runtime flag in this loop
-// measured 1.6 % slower than tracking always.)
-// (Skipping the per-step budget test for waves with budget for a whole walk, at most 10 steps,
-// measured equal.)
-template <bool STATS, bool TRACK>
-__device__ __forceinline__ uint32_t brick_walk(Ray& R, uint64_t bmask, const uint32_t w[3], uint32_t left0, uint32_t& left, bool& solid,
-                                               Stats& st) {
-    // 127 - voxel index (byte 0: the 64-bit shift reads its low 6 bits, 63 - v, which moves the
-    // voxel's bit to bit 63 — one shift and a sign test; the +-1/4/16 moves of a walk stay within
-    // 48..143, so byte 0 never borrows) and steps left (bytes 1-3, biased: 0x80 + left - 1, so a
-    // byte leaves the brick by clearing its top bit, without a borrow) in one register.  The step
-    // keeps its delta instead of the axis: the axis follows from the last delta after the walk.
-    uint32_t pk = (left0 << 8) | (127u - child_slot(w[0], w[1], w[2], 0u));
-    const uint32_t d0 = (uint32_t)(-R.s[0]) - 0x100u, d1 = (uint32_t)(-R.s[1] * 4) - 0x10000u, d2 = (uint32_t)(-R.s[2] * 16) - 0x1000000u;
-    uint32_t dl = 0u;
-    bool go;
-    do {  // one exit: the compiler keeps the state in place (no per-exit copies)
-        solid = (int64_t)(bmask << (pk & 63u)) < 0;
-        go = !solid && R.steps > 0;
-        if (go) {
-            // one DDA step (ray_caster.cpp:70-80) without position updates
-            const bool cx = (R.T[0] < R.T[1]) && (R.T[0] < R.T[2]);
-            const bool cy = !cx && (R.T[1] < R.T[2]);
-            if (TRACK) R.tlast = cx ? R.T[0] : (cy ? R.T[1] : R.T[2]);
-            R.T[0] = cx ? R.T[0] + R.a(0) : R.T[0];
-            R.T[1] = cy ? R.T[1] + R.a(1) : R.T[1];
-            R.T[2] = (cx || cy) ? R.T[2] : R.T[2] + R.a(2);  // (a mask or, not a fourth f64 compare)
-            R.steps--;
-            dl = cx ? d0 : (cy ? d1 : d2);
-            pk += dl;
-            if (STATS) {
-                st.brick_steps++;
-                st.wv_brick += wave_lead();
-            }
-            go = (pk & 0x80808000u) == 0x80808000u;  // every steps-left byte above its bias: inside
-        }
-    } while (go);
-    if (dl != 0u) R.axis = dl == d0 ? 0u : (dl == d1 ? 1u : 2u);
-    left = pk >> 8;
-    return 63u - (pk & 63u);
-}
-
-// Column-ceiling march (round 5).  A descending ray above the ceiling of its 16-column block crosses, cell by cell,
-// only empty voxels until its row reaches that ceiling or it leaves the block; castRayFromCam's DDA (ray_caster.cpp:71-80)
-// takes its x / z / y steps at the crossing values T_k + j * a_k, so every event that matters here is one fma of an
-// integer index: the x (z) event entering the next block, j = the cells left in the block on that axis, and the y event
-// entering the ceiling row c, j = y - 1 - c.  The march walks the blocks the ray's column path crosses (their order
-// follows from the x / z boundary events alone) comparing exact event values, one 32-bit ceiling load per block (the
-// next block's load issued before this one is judged), until the ceiling event comes first or the ray enters a block
-// at or below its ceiling; every voxel entered before that event is then empty, and one closed-form crossing
-// (skip_box) moves the ray to the state right after it — the cell that event enters is the loop's next untested
-// voxel.  This replaces the chain of per-block ceiling moves of a ray's descent (C3: ~6 of its ~11 loop iterations,
-// each a full iteration with its own exact crossing) by one crossing and a few integer / fma steps per block.
-// Linear rays only (every sum exact: `fast` in the non-segment instances), stepping down (R.s[1] < 0); a tie between
-// the x and z boundary events (a block corner) or between a boundary and the ceiling event stops the march there.
-// Returns whether the ray moved.
-// The march's end: ex (skip_box's exits) of the first event whose voxel it could not prove empty.  Returns false when
-// nothing beyond the current voxel is proven (its own row is at or below its block's ceiling).
-template <bool STATS>
-__device__ __forceinline__ bool ceil_march(const CastParams& P, const uint32_t* __restrict__ ceilp, const Ray& R, uint32_t wm, int32_t ex[3],
-                                           Stats& st) {
-    const uint32_t lsh = P.ceil_sh[0];  // the finest level's blocks: 2^lsh columns
-    const uint32_t bm = (1u << lsh) - 1u, rows = (wm + 1u) >> lsh, rm = rows - 1u;
-    const int32_t wy = (int32_t)((uint32_t)R.r[1] & wm);
-    const uint32_t wx = (uint32_t)R.r[0] & wm, wz = (uint32_t)R.r[2] & wm;
-    // per axis the next block-boundary event: its index from the current state (the cells left in the block) and value
-    int32_t jx = (int32_t)(R.s[0] > 0 ? bm - (wx & bm) : (wx & bm)), jz = (int32_t)(R.s[2] > 0 ? bm - (wz & bm) : (wz & bm));
-    double Ex = on_grid(R.T[0], jx, R.a(0)), Ez = on_grid(R.T[2], jz, R.a(2));
-    uint32_t bx = wx >> lsh, bz = wz >> lsh;
-    const uint32_t dx = R.s[0] > 0 ? 1u : rm, dz = R.s[2] > 0 ? 1u : rm;  // (one block on, wrapped)
-    uint32_t cv = ceilp[__umul24(bz, rows) + bx];
-    double Ein = -__builtin_inf();  // the event that entered the current block (none for the first)
-    int32_t ein_axis = -1, ein_j = 0, stop_axis = -1, stop_j = 0;
-    for (int32_t it = 0;; it++) {
-        const bool xn = Ex < Ez;
-        // the next block's ceiling, loaded before this block is judged (the blocks' order follows from x / z alone)
-        const uint32_t nbx = xn ? (bx + dx) & rm : bx, nbz = xn ? bz : (bz + dz) & rm;
-        const uint32_t ncv = ceilp[__umul24(nbz, rows) + nbx];
-        const int32_t jy = wy - 1 - (int32_t)(int16_t)(cv & 0xFFFFu);  // the y event entering the ceiling row
-        const double tc = jy >= 0 ? on_grid(R.T[1], jy, R.a(1)) : -__builtin_inf();
-        if (!(tc > Ein) || it == 1024) {  // the voxel entering this block is at or below its ceiling: end before that event
-            stop_axis = ein_axis;        // (and a bound on the march: its blocks so far are proven)
-            stop_j = ein_j;
-            break;
-        }
-        const double Eexit = xn ? Ex : Ez;
-        // the next boundary lies beyond the budget: only the ceiling event can come first within it
-        const bool far = (xn ? jx : jz) > R.steps;
-        if (!(Eexit < tc) || Ex == Ez || far) {
-            if (far || (!(Ez <= tc && Ez <= Ex) && tc <= Ex)) {  // the first unproven event, in the DDA's order at ties: z, y, x
-                stop_axis = 1;
-                stop_j = jy;
-            } else if (Ez <= tc && Ez <= Ex) {
-                stop_axis = 2;
-                stop_j = jz;
-            } else {
-                stop_axis = 0;
-                stop_j = jx;
-            }
-            break;
-        }
-        if (STATS) st.ceil_moves++;
-        Ein = Eexit;  // on into the next block
-        if (xn) {
-            ein_axis = 0;
-            ein_j = jx;
-            jx += (int32_t)bm + 1;
-            Ex = on_grid(R.T[0], jx, R.a(0));
-        } else {
-            ein_axis = 2;
-            ein_j = jz;
-            jz += (int32_t)bm + 1;
-            Ez = on_grid(R.T[2], jz, R.a(2));
-        }
-        bx = nbx;
-        bz = nbz;
-        cv = ncv;
-    }
-    // (selects on values: a dynamically indexed register array would go through scratch)
-    ex[0] = stop_axis == 0 ? stop_j : R.steps;
-    ex[1] = stop_axis == 1 ? stop_j : R.steps;
-    ex[2] = stop_axis == 2 ? stop_j : R.steps;
-    return stop_axis >= 0;
-}
-
-// A shading ray's DDA state on entering the first block it hits (the cell, crossing values, budget and last step axis):
-// the straight trace before any bounce hands it to the reflection / refraction trace, which resumes from it (trace: T_XS_SAVE / T_XS_RESUME)
-struct RayState {
-    double T[3];
-    int32_t r[3];
-    int32_t steps;
-    uint32_t axis;
-};
-
-// Reflections and refractions of the shading pass (reflectRay / refractRay, low_res.frag:170-240):
-// direction after them, reflection count, finalColorMod (a vec3: liquid tints per channel), and
-// whether the ray was bent (kBent, a bit of the reflection count's word: 28 B per lane in LDS, which with the launch's own
-// path depth lets the shading instances run 7 waves per SIMD).
-constexpr int32_t kBent = 1 << 30;
-struct Bounce {
-    float d[3];
-    int32_t n;  // reflections | kBent
-    float m[3];
-};
-
-// refractRay(vec3, vec3, float, float) (low_res.frag:196-209), n1 = 1.0, n2 = 1.1; dot as
-// ((x + y) + z), no fused operations (-ffp-contract=off)
-__device__ __forceinline__ void refract_dir(float d[3], const float nin[3]) {
-    const float r = 1.0f / 1.1f;
-    float n[3] = {nin[0], nin[1], nin[2]};
-    float c1 = (n[0] * d[0] + n[1] * d[1]) + n[2] * d[2];
-    if (c1 < 0.0f) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) n[k] = -n[k];
-        c1 = (n[0] * d[0] + n[1] * d[1]) + n[2] * d[2];
-    }
-    const float c2 = svo::sqrt_rn(1.0f - r * r * (1.0f - c1 * c1));
-    const float kf = r * c1 - c2;
-#pragma unroll
-    for (int k = 0; k < 3; k++) d[k] = r * d[k] + kf * n[k];
-}
+#include "svo_exact.h"       // the note on exact closed-form skipping, the tests for the rays it covers, Ray, dda_step
+#include "svo_boxes.h"       // forward boxes of empty sibling slots, from the parent's child mask
+#include "svo_skip.h"        // the closed-form crossing of an empty box (skip_box), its counts and exact segments
+#include "svo_stats.h"       // the diagnostics counters and the slots of their buffer (S_*)
+#include "svo_lookup.h"      // the parent in registers, the LDS path, node addressing, the region lookup
+#include "svo_brick.h"       // the brick walk
+#include "svo_ceil_march.h"  // the column-ceiling march before the loop
+#include "svo_bounce.h"      // the shading pass's bounce state and refraction
 
 __host__ __device__ constexpr int32_t dirs_sign(int DIRS, int k) { return DIRS == 0 ? 0 : (((DIRS - 1) >> k) & 1) ? -1 : 1; }
 
@@ -1292,31 +544,31 @@ __device__ __forceinline__ Hit trace(const CastParams& P, const Mem& mem, const 
         const uint32_t work = st.lookups + st.brick_steps + st.plain_steps;
         const uint32_t wmax = wave_max(work), wsum = wave_sum(work);
         if ((threadIdx.x & 63) == 0) {
-            atomicAdd(P.stats + 7, (unsigned long long)wsum);
-            atomicAdd(P.stats + 8, (unsigned long long)wmax * 64ull);
+            atomicAdd(P.stats + S_LANE_WORK, (unsigned long long)wsum);
+            atomicAdd(P.stats + S_WAVE_MAX_WORK_X64, (unsigned long long)wmax * 64ull);
         }
-        atomicAdd(P.stats + 0, 1ull);
-        atomicAdd(P.stats + 1, (unsigned long long)st.lookups);
-        atomicAdd(P.stats + 2, (unsigned long long)st.loads);
-        atomicAdd(P.stats + 3, (unsigned long long)st.skips);
-        atomicAdd(P.stats + 4, (unsigned long long)st.skip_out);
-        atomicAdd(P.stats + 5, (unsigned long long)st.brick_steps);
-        atomicAdd(P.stats + 6, (unsigned long long)st.plain_steps);
-        for (int k = 0; k < 4; k++) atomicAdd(P.stats + 9 + k, (unsigned long long)st.skip_by_sh[k]);
-        atomicAdd(P.stats + 13, (unsigned long long)st.bricks);
-        atomicAdd(P.stats + 14, (unsigned long long)st.wv_iters);
-        atomicAdd(P.stats + 15, (unsigned long long)st.wv_brick);
-        atomicAdd(P.stats + 17, (unsigned long long)st.root_starts);
-        atomicAdd(P.stats + 18, (unsigned long long)st.cache_empty);
-        atomicAdd(P.stats + 19, (unsigned long long)st.wv_skips);
-        atomicAdd(P.stats + 20, (unsigned long long)st.wv_descents);
-        atomicAdd(P.stats + 21, (unsigned long long)st.path_starts);
-        if (st.no_progress) atomicAdd(P.stats + 16, (unsigned long long)st.no_progress);
-        atomicAdd(P.stats + 23, (unsigned long long)st.ceil_moves);
-        atomicAdd(P.stats + 24, (unsigned long long)st.above_top);
-        atomicAdd(P.stats + 25, (unsigned long long)st.bends);
-        atomicAdd(P.stats + 26, (unsigned long long)st.tints);
-        atomicAdd(P.stats + 27, (unsigned long long)st.tint_iters);
+        atomicAdd(P.stats + S_RAYS, 1ull);
+        atomicAdd(P.stats + S_LOOKUPS, (unsigned long long)st.lookups);
+        atomicAdd(P.stats + S_LOADS, (unsigned long long)st.loads);
+        atomicAdd(P.stats + S_SKIPS, (unsigned long long)st.skips);
+        atomicAdd(P.stats + S_SKIP_OUT, (unsigned long long)st.skip_out);
+        atomicAdd(P.stats + S_BRICK_STEPS, (unsigned long long)st.brick_steps);
+        atomicAdd(P.stats + S_PLAIN_STEPS, (unsigned long long)st.plain_steps);
+        for (int k = 0; k < 4; k++) atomicAdd(P.stats + S_SKIPS_4 + k, (unsigned long long)st.skip_by_sh[k]);
+        atomicAdd(P.stats + S_BRICKS, (unsigned long long)st.bricks);
+        atomicAdd(P.stats + S_WV_ITERS, (unsigned long long)st.wv_iters);
+        atomicAdd(P.stats + S_WV_BRICK, (unsigned long long)st.wv_brick);
+        atomicAdd(P.stats + S_ROOT_STARTS, (unsigned long long)st.root_starts);
+        atomicAdd(P.stats + S_CACHE_EMPTY, (unsigned long long)st.cache_empty);
+        atomicAdd(P.stats + S_WV_SKIPS, (unsigned long long)st.wv_skips);
+        atomicAdd(P.stats + S_WV_DESCENTS, (unsigned long long)st.wv_descents);
+        atomicAdd(P.stats + S_PATH_STARTS, (unsigned long long)st.path_starts);
+        if (st.no_progress) atomicAdd(P.stats + S_NO_PROGRESS, (unsigned long long)st.no_progress);
+        atomicAdd(P.stats + S_CEIL_MOVES, (unsigned long long)st.ceil_moves);
+        atomicAdd(P.stats + S_ABOVE_TOP, (unsigned long long)st.above_top);
+        atomicAdd(P.stats + S_BENDS, (unsigned long long)st.bends);
+        atomicAdd(P.stats + S_TINTS, (unsigned long long)st.tints);
+        atomicAdd(P.stats + S_TINT_ITERS, (unsigned long long)st.tint_iters);
         // per-ray work (offline analysis, bench.py SVO_RAY_WORK): 16-bit fields, lookups | iterations | brick steps | node loads
         if (ray_work)
             *ray_work = (unsigned long long)min(st.lookups, 65535u) | ((unsigned long long)min(st.iters, 65535u) << 16) |

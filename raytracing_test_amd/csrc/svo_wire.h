@@ -12,7 +12,7 @@
 // record's pixel, so it regenerates the ray (raygen_pixel, dda_axis, the same code the kernel runs) and
 // recovers the step signs, the position (cell + s n), the steps left (a hit: steps - n_x - n_y - n_z) and
 // t.  From such origins deltaPos starts at a, 0, a/2, 3a/2 or -a/2 and every crossing sum the DDA takes is
-// exact (svo_trace.h, lin_origin), so after n steps on the last axis its deltaPos is fma(n, a, T0) —
+// exact (svo_skip.h, lin_origin), so after n steps on the last axis its deltaPos is fma(n, a, T0) —
 // the double the kernel holds — and t = that - a (an infinite absDelta keeps it as is: inf or NaN, as
 // the kernel's recovery does).
 #pragma once

@@ -1,4 +1,4 @@
-"""Directed rays: the equalities of svo_trace.h's closed-form crossings, aimed at instead of hoped for.
+"""Directed rays: the equalities of svo_skip.h's closed-form crossings, aimed at instead of hoped for.
 
 skip_box (lexicographic minimum of three exit events, ties z < y < x), count_est (f32 estimate + fix-up), seg_cap
 (exact segments by binade), ceil_march and the in-loop ceiling boxes (tc > Ein, Ex == Ez, Ez <= tc && Ez <= Ex), the

@@ -459,7 +459,7 @@ def test_depth12_budget_ends_in_air(rt, depth12, oracle12, pose, steps):
 @pytest.mark.parametrize("org", [(4.37, 90.61, 4.23), (-7.3, 88.125, 1000.01)])
 def test_depth12_fractional_camera(rt, depth12, oracle12, org):
     """C3 from non-integral camera positions, S = 16384: the rays are not linear (their crossings
-    round once per binade), so the kernel crosses empty regions in exact segments (svo_trace.h,
+    round once per binade), so the kernel crosses empty regions in exact segments (svo_skip.h,
     seg_cap).  Sampled pixels (top and bottom rows, the horizon band) against the oracle; the whole
     frame identical to the voxel-by-voxel path; still O(1) crossings (not voxel stepping)."""
     T = oracle12

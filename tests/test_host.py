@@ -23,6 +23,30 @@ def test_abi_exports_every_declared_symbol(rt):
     assert rt.lib().svo_version() == 7
 
 
+def test_stat_slots_mirror_stat_names(rt):
+    """The kernel's counter slots (the S_* enum of csrc/svo_stats.h) and the host's STAT_NAMES are one list: as many
+    entries, slot k named after STAT_NAMES[k], all within the buffer's header."""
+    src = open(os.path.join(ROOT, "raytracing_test_amd", "csrc", "svo_stats.h")).read()
+    body = re.search(r"enum\s*:\s*int32_t\s*\{([^}]*S_RAYS[^}]*)\}", src).group(1)
+    body = re.sub(r"//[^\n]*", "", body)
+    slots, nxt = [], 0
+    for name, val in re.findall(r"\b(S_\w+)\s*(?:=\s*(\d+))?\s*,", body):
+        nxt = int(val) if val else nxt
+        slots.append((name, nxt))
+        nxt += 1
+    assert [v for _, v in slots] == list(range(len(slots)))  # (the pinned values agree with the positions)
+    assert len(slots) == len(rt.STAT_NAMES)
+    assert dict(slots)["S_NO_PROGRESS"] == 16 and dict(slots)["S_AO_NODE_LOADS"] == 22 and slots[-1] == ("S_TINT_ITERS", 27)
+    # the kernel's names follow the Stats fields; where the host's spelling differs:
+    other = {"S_LOADS": "node_loads", "S_SKIP_OUT": "skip_budget_out", "S_WV_ITERS": "wave_iters", "S_WV_BRICK": "wave_brick_steps",
+             "S_WV_SKIPS": "wave_skips", "S_WV_DESCENTS": "wave_descents", "S_ABOVE_TOP": "iters_above_top"}
+    for (name, k), py in zip(slots, rt.STAT_NAMES):
+        assert other.get(name, name[2:].lower()) == py, (k, name, py)
+    hdr = open(os.path.join(ROOT, "include", "svo_rt.h")).read()
+    header = int(re.search(r"^#define SVO_STATS_HEADER (\d+)", hdr, re.M).group(1))
+    assert len(slots) <= header == rt.STATS_HEADER
+
+
 def test_product_noise_matches_reference_golden(rt):
     g = np.load(os.path.join(GOLD, "noise_ref.npz"))
     for seed in np.unique(g["seed"]):

@@ -1,4 +1,4 @@
-"""The exactness claim behind the kernel's segment-bounded crossings (svo_trace.h: seg_cap), checked
+"""The exactness claim behind the kernel's segment-bounded crossings (svo_skip.h: seg_cap), checked
 on the CPU: from a DDA state (T, a) as dda_axis and later additions produce it, the crossings
 0 .. seg_cap + 1 computed in closed form — one rounding of the exact T + i*a, as fma(i, a, T) does —
 equal castRayFromCam's iterated double sums T += a (ray_caster.cpp:70-80).  seg_cap is restated here
@@ -72,7 +72,7 @@ def test_segment_cap_is_exact():
 
 
 def _count_est(T, af, inva, V):
-    # svo_trace.h count_est: m = cvt_u32(fma_f32(f32(V) - f32(T), inva, 0.5)) (the f32 fma emulated
+    # svo_skip.h count_est: m = cvt_u32(fma_f32(f32(V) - f32(T), inva, 0.5)) (the f32 fma emulated
     # as the exact product plus 1/2 in double, rounded to f32 once more; v_cvt_u32_f32 truncates and
     # saturates at 0)
     x = np.float32(np.float32(V) - np.float32(T))

@@ -1,4 +1,4 @@
-"""How much brick walking the brick pass-through can remove (svo_trace.h, skip_box PASS): C3 rays
+"""How much brick walking the brick pass-through can remove (svo_skip.h, skip_box PASS): C3 rays
 (the C1 pose over the 4096^2 genWorld terrain, S = 16384) traced voxel by voxel in Python with
 castRayFromCam's double DDA (src/ray_caster.cpp:54-87); each maximal run of voxels inside one mixed 4^3
 brick is a brick visit.  A visit that does not end in a hit passes when no solid voxel of the brick lies

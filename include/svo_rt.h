@@ -29,7 +29,8 @@ extern "C" {
                              and removed); 7: 8-B compact wire records, svo_wire_bytes / svo_cast_wire /
                              svo_wire_scatter / svo_exchange_wire.  Entry points added since keep the number and are
                              detected by symbol (dlsym / hasattr): svo_build_volume_gpu, svo_tree_read_volume,
-                             svo_volume_classify_pass */
+                             svo_volume_classify_pass, svo_tree_patch_volume_gpu, svo_tree_garbage,
+                             svo_tree_patch_times */
 
 enum {
     SVO_OK = 0,
@@ -150,8 +151,8 @@ int svo_build_heightfield_gpu(int32_t levels, int32_t width, int32_t length, con
    view, palette[0] not the empty block; SVO_ERANGE: n_palette outside 1..65535, a voxel id >= n_palette (found on
    the device by the first pass; nothing is emitted); SVO_ENOMEM: no scratch.  Arguments are checked before the first
    HIP call.  The device is synchronised on entry (the volume may come from any stream); the build runs on the null
-   stream.  Such a tree has no svo_world behind it: svo_tree_update stays a world-only path, a volume tree is rebuilt
-   from a new volume, not patched. */
+   stream.  Such a tree has no svo_world behind it: svo_tree_update stays a world-only path, and a volume tree is
+   changed in HBM by svo_tree_patch_volume_gpu. */
 typedef struct {
     int32_t levels;              /* extent 4^levels per axis; 2..7 like the other GPU builders */
     int32_t nx, ny, nz;          /* voxels; voxels[((int64)z * ny + y) * nx + x] — a contiguous (nz, ny, nx) tensor */
@@ -173,6 +174,41 @@ int svo_tree_read_volume(const svo_tree* t, const int32_t origin[3], int32_t nx,
 /* diagnostics (tools/volume_build_timing.py): svo_build_volume_gpu's first pass alone — the level-1 classification,
    which reads the whole volume — run `runs` times into scratch, each timed by HIP events: ms[0 .. runs-1] */
 int svo_volume_classify_pass(const svo_volume_desc* v, int32_t runs, float* ms);
+/* Patch a resident tree from a dense box of voxels in HBM, on the device: after the call the tree's content inside the
+   box is exactly `voxels` (ids the tree's view does not hold are stored empty, as in svo_build_volume_gpu); everything
+   outside the box is as before.  Any uploaded tree (volume-, terrain- or world-built), either view, any size (nodes are
+   read through 64-bit addresses).  Regions the box does not meet keep their records and subtrees; aligned regions wholly
+   inside the box are emitted canonically from the box (svo_build_volume_gpu's class pyramid over the box, whose first
+   pass reads the box once and checks the ids); regions the box cuts are re-emitted one level down, in new child blocks
+   appended to the arrays, down to bricks classified from their 64 composite voxels (a brick that stores none clears its
+   slot bit).  Only one record is rewritten in place: that of the deepest interior node whose region holds the box (the
+   anchor).  As after svo_tree_update, the result is the tree's content, not its canonical layout: cut interior regions
+   are not re-collapsed when they end up uniform or empty (records with mask 0 may result; traversal is unaffected).  A
+   box that is the whole extent is a full build: the arrays restart and nothing stays superseded.
+   The device arrays are reallocated (with the slack of a fresh upload) only when the appended tail would not fit; the
+   host image, the column ceilings and svo_tree_garbage's counts are brought up to date.  A world-built tree patched
+   this way no longer follows its svo_world: svo_tree_update on it returns SVO_ESTATE.
+   SVO_EINVAL: a NULL pointer, a non-positive dimension, a box that leaves the extent; SVO_ESTATE: the tree is not
+   uploaded, or has host edits not yet synced (svo_tree_sync); SVO_ERANGE: an id >= the tree's palette size (found by
+   the first pass: nothing is appended, and the tree is unchanged on host and device), arrays that would pass 2^32
+   elements, a tree of one level; SVO_ENOMEM: no scratch.  Arguments are checked before the first HIP call.
+   The device is synchronised on entry (the box may come from any stream, and records and ceilings are rewritten in
+   place: svo_tree_sync's contract: call it between frames); the call is complete on return.
+   Not done here: palette growth (ids are the tree's own palette), and compaction of superseded records
+   (svo_tree_garbage tells the caller when a rebuild, e.g. svo_tree_read_volume + svo_build_volume_gpu, pays). */
+typedef struct {
+    int32_t nx, ny, nz;        /* voxels[((int64)z * ny + y) * nx + x], as svo_volume_desc */
+    int32_t origin[3];         /* world position of voxels[0]; origin >= 0, origin + n <= extent (no wrap) */
+    const uint16_t* voxels;    /* DEVICE pointer on the tree's device: ids of the tree's own palette, 0 = empty */
+} svo_volume_box;
+int svo_tree_patch_volume_gpu(svo_tree* t, const svo_volume_box* box);
+/* node records and material entries superseded by edits (svo_tree_update, svo_tree_patch_volume_gpu) since the last
+   full build: still in the arrays, no longer reachable (either may be NULL) */
+int svo_tree_garbage(const svo_tree* t, uint64_t* nodes, uint64_t* mats);
+/* diagnostics (tools/volume_patch_timing.py): host-clock milliseconds of the tree's last svo_tree_patch_volume_gpu, after
+   its entry synchronisation: ms[0] the device passes (pyramid, count and write passes into scratch), ms[1] the commit to
+   the arrays and the copy back to the host image, ms[2] the host's ceiling update (with the tree's top row) */
+int svo_tree_patch_times(const svo_tree* t, double ms[3]);
 int svo_tree_get_info(const svo_tree* t, svo_tree_info* out);
 /* palette entry `id` (id 0 = empty block) */
 int svo_tree_palette(const svo_tree* t, uint32_t id, svo_block* out);

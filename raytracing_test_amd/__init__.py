@@ -126,6 +126,12 @@ class VolumeDesc(C.Structure):
                 ("device", C.c_int32)]
 
 
+class VolumeBox(C.Structure):
+    """svo_volume_box: a dense (nz, ny, nx) box of a tree's own palette ids in HBM, placed at `origin` of its world"""
+
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("origin", C.c_int32 * 3), ("voxels", C.c_void_p)]
+
+
 class Hits(C.Structure):
     _fields_ = [("pos_steps", C.c_void_p), ("t", C.c_void_p), ("info", C.c_void_p), ("ao", C.c_void_p)]
 
@@ -156,6 +162,7 @@ ABI_SYMBOLS = (
     "svo_tree_save", "svo_tree_load", "svo_wire_bytes", "svo_cast_wire", "svo_wire_scatter", "svo_exchange_wire", "svo_tree_ceilings",
     "svo_tree_guard_trips", "svo_ceiling_layout", "svo_tree_device_ceilings", "svo_tree_device_ceiling_quads", "svo_tree_schedule", "svo_cast_ray_from_cam_async",
     "svo_build_id", "svo_build_volume_gpu", "svo_tree_read_volume", "svo_volume_classify_pass",
+    "svo_tree_patch_volume_gpu", "svo_tree_garbage", "svo_tree_patch_times",
 )
 
 
@@ -236,7 +243,10 @@ def lib():
                      ("svo_cast_ray_from_cam_async", [vp, f3, f3, i32, vp, vp]),
                      ("svo_build_volume_gpu", [C.POINTER(VolumeDesc), C.POINTER(vp)]),
                      ("svo_tree_read_volume", [vp, C.POINTER(i32), i32, i32, i32, vp, vp]),
-                     ("svo_volume_classify_pass", [C.POINTER(VolumeDesc), i32, C.POINTER(f32)])):
+                     ("svo_volume_classify_pass", [C.POINTER(VolumeDesc), i32, C.POINTER(f32)]),
+                     ("svo_tree_patch_volume_gpu", [vp, C.POINTER(VolumeBox)]),
+                     ("svo_tree_garbage", [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+                     ("svo_tree_patch_times", [vp, C.POINTER(C.c_double)])):
         if hasattr(L, name):
             getattr(L, name).argtypes = at
     L.svo_build_terrain.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
@@ -490,9 +500,9 @@ class Tree:
         return cls(t)
 
     @staticmethod
-    def volume_desc(levels, voxels, palette, origin=(0, 0, 0), view=VIEW_SOLID, device=0):
-        """(VolumeDesc, the device tensor it points to) for volume_gpu's arguments, validated: ValueError for a wrong
-        dtype, rank or device or a non-contiguous tensor, before the library is called"""
+    def _device_volume(voxels, device):
+        """the (nz, ny, nx) id tensor on cuda:`device` that a volume argument stands for (a numpy uint16 array is
+        uploaded), validated: ValueError for a wrong dtype, rank or device or a non-contiguous tensor"""
         torch = _torch()
         if isinstance(voxels, np.ndarray):
             if voxels.dtype != np.uint16 or voxels.ndim != 3:
@@ -508,6 +518,13 @@ class Tree:
             raise ValueError("voxels: the tensor must be contiguous")
         if not voxels.is_cuda or voxels.device.index != device:
             raise ValueError("voxels: the tensor must live on cuda:%d, not %s" % (device, voxels.device))
+        return voxels
+
+    @staticmethod
+    def volume_desc(levels, voxels, palette, origin=(0, 0, 0), view=VIEW_SOLID, device=0):
+        """(VolumeDesc, the device tensor it points to) for volume_gpu's arguments, validated: ValueError for a wrong
+        dtype, rank or device or a non-contiguous tensor, before the library is called"""
+        voxels = Tree._device_volume(voxels, device)
         if len(origin) != 3:
             raise ValueError("origin: three integers")
         pal = (Block * max(1, len(palette)))()
@@ -531,12 +548,47 @@ class Tree:
         to `device`.  voxels: a contiguous CUDA tensor (nz, ny, nx) of torch.uint16 / torch.int16 (the bits are the ids;
         0 = empty), or a numpy uint16 array of that shape (uploaded through torch); palette: [(flags, color, metadata)]
         as Tree.palette() returns it, entry 0 the empty block; origin: the world position of voxels[0, 0, 0] as
-        (x, y, z).  Voxels outside the box are empty.  A volume tree is rebuilt, not patched (update() needs a World)."""
+        (x, y, z).  Voxels outside the box are empty.  Such a tree has no World behind it (update() needs one): it is
+        changed in HBM by patch_volume()."""
         d, keep = cls.volume_desc(levels, voxels, palette, origin, view, device)
         h = C.c_void_p()
         _check(lib().svo_build_volume_gpu(C.byref(d), C.byref(h)), "svo_build_volume_gpu")
         del keep
         return cls(h)
+
+    def patch_volume(self, voxels, origin):
+        """svo_tree_patch_volume_gpu: replace this (uploaded) tree's content inside a box by `voxels`, on the device.
+        voxels: a contiguous CUDA tensor (nz, ny, nx) of torch.uint16 / torch.int16 on the tree's device holding ids of
+        the tree's own palette (0 = empty; ids its view does not store become empty), or a numpy uint16 array of that
+        shape (uploaded through torch); origin: the world position of voxels[0, 0, 0] as (x, y, z).  Everything outside
+        the box stays as it is; the host image, the ceilings and garbage() are brought up to date, and the call is
+        complete on return.  Any uploaded tree may be patched; a World-built one no longer follows its World afterwards
+        (update() then fails)."""
+        dev = self.info().device
+        if dev < 0:
+            raise SvoError("svo_tree_patch_volume_gpu failed (-4): tree not uploaded (svo_upload)")
+        voxels = self._device_volume(voxels, dev)
+        if len(origin) != 3:
+            raise ValueError("origin: three integers")
+        b = VolumeBox()
+        b.nz, b.ny, b.nx = (int(n) for n in voxels.shape)
+        b.origin[:] = [int(o) for o in origin]
+        b.voxels = voxels.data_ptr()
+        _check(lib().svo_tree_patch_volume_gpu(self._h, C.byref(b)), "svo_tree_patch_volume_gpu")
+        return self
+
+    def garbage(self):
+        """svo_tree_garbage: (node records, material entries) superseded by update() / patch_volume() since the last
+        full build: when they outweigh the tree, a rebuild pays"""
+        n, m = C.c_uint64(), C.c_uint64()
+        _check(lib().svo_tree_garbage(self._h, C.byref(n), C.byref(m)), "svo_tree_garbage")
+        return n.value, m.value
+
+    def patch_times(self):
+        """svo_tree_patch_times: host-clock ms of the last patch_volume() — (device passes, commit + host image, ceilings)"""
+        ms = (C.c_double * 3)()
+        _check(lib().svo_tree_patch_times(self._h, ms), "svo_tree_patch_times")
+        return tuple(ms)
 
     def read_volume(self, origin, shape, out=None, stream=None):
         """svo_tree_read_volume: the palette ids this (uploaded) tree stores in the box of `shape` = (nz, ny, nx) voxels

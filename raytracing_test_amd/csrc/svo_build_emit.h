@@ -269,6 +269,8 @@ int emit_tree(const S& T, int32_t levels, uint32_t root_class, svo_tree* t, Pool
     if (rc) return rc;
     HIP_TRY(hipMemcpy(dn, nodes, used * sizeof(Node), hipMemcpyDeviceToDevice), SVO_EDEVICE);
     if (n_mats) HIP_TRY(hipMemcpy(dm, mats, n_mats * sizeof(uint16_t), hipMemcpyDeviceToDevice), SVO_EDEVICE);
+    t->nodes.reserve(ncap);  // (the host image with the device arrays' slack: appended tails do not move it)
+    t->mats.reserve(mcap);
     t->nodes.resize(used);
     t->mats.resize(n_mats);
     HIP_TRY(hipMemcpy(t->nodes.data(), dn, used * sizeof(Node), hipMemcpyDeviceToHost), SVO_EDEVICE);

@@ -85,7 +85,7 @@ static int upload_ceilings(svo_tree* t) {
 
 // after edits: only the columns svo_tree_update touched are recomputed (tree walks restricted to them), and only the
 // rows of the tables that changed travel, into the device buffers already there
-static int sync_ceilings(svo_tree* t) {
+int svo::sync_ceilings(svo_tree* t) {
     if (t->ceil_dirty.empty()) return SVO_OK;
     if (t->ceil_levels == 0 || !t->d_ceil) {
         t->ceil_dirty.clear();
@@ -99,7 +99,7 @@ static int sync_ceilings(svo_tree* t) {
         try {
             ceil_tables_update(t, n, r, zr, qr);
         } catch (const std::bad_alloc&) {
-            SVO_FAIL(SVO_ENOMEM, "svo_tree_sync: column ceilings: out of host memory");
+            SVO_FAIL(SVO_ENOMEM, "column ceilings: out of host memory");
         }
         {
             const int64_t rows = (int64_t)1 << (2 * (t->levels - kCeilK0));

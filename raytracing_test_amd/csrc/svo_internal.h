@@ -82,6 +82,12 @@ struct svo_tree {
     uint64_t synced_nodes = 0, synced_mats = 0;  // prefix of nodes / mats already in HBM
     std::vector<uint32_t> dirty_nodes;           // rewritten in place below synced_nodes
     bool palette_dirty = false, full_upload = false;
+    // svo_tree_patch_volume_gpu has changed the tree: it no longer mirrors the svo_world it was built from, and
+    // svo_tree_update refuses it
+    bool volume_patched = false;
+    // host-clock milliseconds of the last patch (svo_tree_patch_times): the device passes up to the totals, the commit and
+    // the copy back to the host image, the ceiling update with tree_top_y
+    double patch_ms[3] = {0.0, 0.0, 0.0};
     uint64_t dev_node_cap = 0, dev_mat_cap = 0, dev_pal_n = 0;  // device allocations (elements)
     // highest voxel row holding a stored voxel (tree_top_y; -1: empty tree), cached until an edit
     mutable int32_t top_y = -1;
@@ -151,4 +157,7 @@ void tree_release_device(svo_tree* t);  // svo_device.hip
 // take over device arrays built on `device` (node_cap / mat_cap elements allocated, the host image
 // already equal to their first nodes.size() / mats.size() elements): svo_device.hip
 int adopt_device(svo_tree* t, int32_t device, void* d_nodes, uint64_t node_cap, void* d_mats, uint64_t mat_cap);
+// the ceiling tables over the rectangles of svo_tree.ceil_dirty recomputed from the host image, the changed rows sent to the
+// device buffers already there (svo_tree_sync's last step, and svo_tree_patch_volume_gpu's): svo_device.hip
+int sync_ceilings(svo_tree* t);
 }

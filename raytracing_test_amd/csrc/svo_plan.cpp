@@ -239,6 +239,82 @@ bool tree_unsynced(const svo_tree* t) {
            t->palette_dirty || !t->ceil_dirty.empty();
 }
 
+PatchAnchor patch_anchor(const Node* nodes, int32_t levels, const int32_t lo[3], const int32_t hi[3]) {
+    PatchAnchor a{0u, 0, {0, 0, 0}, P_NODE, 0u, true};
+    const int32_t e = 1 << (2 * levels);
+    for (int i = 0; i < 3; i++) a.whole = a.whole && lo[i] == 0 && hi[i] == e;
+    if (node_kind(nodes[0].info) != K_INTERIOR) {  // a lone SOLID root (a BRICK root: a tree of one level, which is not patched)
+        a.kind = P_UNIFORM;
+        a.old = node_material(nodes[0].info);
+        return a;
+    }
+    while (!a.whole && a.depth < levels - 2) {  // (a child at depth levels - 1 is a BRICK or SOLID record)
+        const int32_t cs = 1 << (2 * (levels - 1 - a.depth));
+        int32_t c[3];
+        bool inside = true, fills = true;
+        for (int i = 0; i < 3; i++) {
+            c[i] = a.o[i] + ((lo[i] - a.o[i]) / cs) * cs;  // the child region holding the box's first voxel
+            inside = inside && hi[i] <= c[i] + cs;
+            fills = fills && lo[i] == c[i] && hi[i] == c[i] + cs;
+        }
+        if (!inside || fills) break;
+        const Node& n = nodes[a.node];
+        const uint32_t sl = (uint32_t)((((c[2] - a.o[2]) / cs) << 4) | (((c[1] - a.o[1]) / cs) << 2) | ((c[0] - a.o[0]) / cs));
+        if (!((n.mask >> sl) & 1ull)) break;
+        const uint32_t ci = packed_index(n, sl);
+        if (node_kind(nodes[ci].info) != K_INTERIOR) break;
+        a.node = ci;
+        a.depth++;
+        for (int i = 0; i < 3; i++) a.o[i] = c[i];
+    }
+    a.old = a.node;
+    return a;
+}
+
+namespace {
+struct Superseded {
+    const Node* nodes;
+    int32_t levels;
+    const int32_t *lo, *hi;
+    uint64_t n_nodes = 0, n_mats = 0;
+    // node ni's record is replaced: what hangs below it.  all: the region lies wholly inside the box
+    void walk(uint32_t ni, const int32_t o[3], int depth, bool all) {
+        const Node& n = nodes[ni];
+        const uint32_t kind = node_kind(n.info);
+        if (kind == K_SOLID) return;
+        if (kind == K_BRICK) {
+            if (!(n.info & K_UNIFORM)) n_mats += (uint64_t)__builtin_popcountll(n.mask);
+            return;
+        }
+        n_nodes += (uint64_t)__builtin_popcountll(n.mask);
+        const int32_t cs = 1 << (2 * (levels - 1 - depth));
+        uint64_t m = n.mask;
+        uint32_t ci = n.ref;
+        while (m) {
+            const uint32_t sl = (uint32_t)__builtin_ctzll(m);
+            m &= m - 1;
+            const uint32_t c = ci++;
+            const int32_t co[3] = {o[0] + (int32_t)(sl & 3u) * cs, o[1] + (int32_t)((sl >> 2) & 3u) * cs, o[2] + (int32_t)(sl >> 4) * cs};
+            bool out = false, in = true;
+            for (int i = 0; i < 3; i++) {
+                out = out || co[i] + cs <= lo[i] || co[i] >= hi[i];
+                in = in && co[i] >= lo[i] && co[i] + cs <= hi[i];
+            }
+            if (all || in) walk(c, co, depth + 1, true);
+            else if (!out) walk(c, co, depth + 1, false);  // (outside the box: the copied record keeps its subtree)
+        }
+    }
+};
+}  // namespace
+
+void patch_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const int32_t lo[3], const int32_t hi[3], uint64_t* n_nodes,
+                      uint64_t* n_mats) {
+    Superseded s{nodes, levels, lo, hi};
+    s.walk(a.node, a.o, a.depth, a.whole);
+    *n_nodes = s.n_nodes;
+    *n_mats = s.n_mats;
+}
+
 SchedPlan sched_decide(svo_tree::Sched& s, int64_t blocks, const int64_t sig[7], const float cam[6]) {
     if (s.blocks != blocks || !std::equal(sig, sig + 7, s.sig)) {
         s.blocks = blocks;

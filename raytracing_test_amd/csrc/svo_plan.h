@@ -45,6 +45,32 @@ std::vector<std::pair<uint32_t, uint32_t>> dirty_runs(std::vector<uint32_t>& dir
 // the host image holds something its copy in HBM does not (svo_tree_sync would move data)
 bool tree_unsynced(const svo_tree* t);
 
+// svo_tree_patch_volume_gpu (svo_patch_volume.hip) replaces the content of the box [lo, hi) of a resident tree.  What a
+// region held before the patch, as the patch's work items carry it:
+enum : uint32_t {
+    P_PLAIN = 0u,    // nothing: the region lies wholly inside the box and is emitted from the box alone
+    P_NODE = 1u,     // the record nodes[old] (INTERIOR above the brick level, BRICK at it)
+    P_UNIFORM = 2u,  // material `old` throughout (a K_SOLID record, or a region below one)
+    P_EMPTY = 3u,    // nothing stored (a clear slot bit, or a region below one)
+};
+// Where the patch starts, as svo_tree_update's walk: down from the root while the box lies inside one child region without
+// filling it and that child's record is K_INTERIOR.  The node reached is the anchor, the only record rewritten in place;
+// every child of it that the box meets is cut by the box or wholly inside it.  A root that is a lone K_SOLID record is the
+// anchor itself (kind P_UNIFORM: it becomes interior).  whole: the box is the whole extent, and the root itself is replaced.
+struct PatchAnchor {
+    uint32_t node;   // index of the anchor's record
+    int32_t depth;   // its depth: the region is 4^(levels - depth) voxels wide
+    int32_t o[3];    // the region's first voxel
+    uint32_t kind;   // P_NODE, or P_UNIFORM for a lone K_SOLID root
+    uint32_t old;    // the material of P_UNIFORM (P_NODE: node)
+    bool whole;
+};
+PatchAnchor patch_anchor(const Node* nodes, int32_t levels, const int32_t lo[3], const int32_t hi[3]);
+// the node records and material entries the patch supersedes below the anchor: the child block of every interior node the
+// box cuts (it is rewritten at the tail), every subtree wholly inside the box, the material run of every brick the box meets
+void patch_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const int32_t lo[3], const int32_t hi[3], uint64_t* n_nodes,
+                      uint64_t* n_mats);
+
 // A schedule predicts a frame from the last one: a camera that turned more than kSchedTurn or moved more than kSchedMove
 // voxels since runs the default order (and re-primes).  Measured (tools/shade_motion.py, r04_ax): a still view 0.462 ->
 // 0.368 ms; 0.25 deg + 0.14 voxels per frame 0.400 -> 0.395; 2 deg per frame 0.292 -> 0.374 and a cut every frame

@@ -93,7 +93,9 @@ int svo_world_node_count(const svo_world* w, uint64_t* nodes);
 /* batched getBlock over n positions (xyz = 3 x int32 each) — the traverseTree batch lookup of
    tetrahexa_tree.cpp:43-111, made usable */
 int svo_get_blocks(const svo_world* w, const int32_t* xyz, int64_t n, svo_block* out);
-/* batched putBlock of n blocks, all at `level`, applied in order */
+/* batched putBlock of n blocks, all at `level`, applied in order.  It stops at the first block that fails and returns
+   that block's error: on SVO_ERANGE (a 65535th distinct block) the blocks before it are stored, it and the blocks
+   after it are not, and the palette is unchanged by it */
 int svo_put_blocks(svo_world* w, const int32_t* xyz, const svo_block* blocks, int64_t n, int32_t level);
 /* OpenSimplex 2D (include/OpenSimplexNoise.cpp:77-208) for n points, and genWorld's column tops
    (world_gen.cpp:22) for x in [0,width), z in [0,length): out[x*length + z] */

@@ -93,15 +93,27 @@ def _puts():
     return out
 
 
-def hall(rt, oracle_mod):
-    """(rt.World, oracle Tree) holding the same blocks"""
+FILLER_AT = (700, 700, 700)                        # a voxel the hall leaves empty: palette_cases.preload's scratch voxel
+
+
+def hall(rt, oracle_mod, preload=0, T=None):
+    """(rt.World, oracle Tree) holding the same blocks.  preload: that many throw-away materials interned first
+    (palette_cases.preload), so the hall's palette ids start at preload + 1; the oracle stores blocks per voxel and has no
+    palette, so its tree is the same for any preload: pass a tree built earlier as T to share it (it is returned as is)"""
     w = rt.World(LEVELS)
-    T = oracle_mod.Tree(LEVELS)
-    oracle_mod.lib().orc_init_clean_root(T.h)
+    if preload:
+        import palette_cases
+
+        palette_cases.preload(w, preload, FILLER_AT)
+    build_oracle = T is None
+    if build_oracle:
+        T = oracle_mod.Tree(LEVELS)
+        oracle_mod.lib().orc_init_clean_root(T.h)
     for pts, flags, colours, level in _puts():
         w.put_blocks(pts, flags, colours, level=level)
-        for (x, y, z), f, c in zip(pts.tolist(), flags.tolist(), colours.tolist()):
-            assert T.put_block(x, y, z, f, c, 0.0, level) == 0
+        if build_oracle:
+            for (x, y, z), f, c in zip(pts.tolist(), flags.tolist(), colours.tolist()):
+                assert T.put_block(x, y, z, f, c, 0.0, level) == 0
     return w, T
 
 

@@ -65,10 +65,10 @@ def no_guard(solid, scene):
     assert solid.guard_trips() == 0 and scene.guard_trips() == 0
 
 
-def check(rt, pal_tree, rgba, out, ref, label):
-    """one launch against the oracle: the records (when the launch wrote them) and the colours"""
+def check(rt, pal_tree, rgba, out, ref, label, palette=None):
+    """one launch against the oracle: the records (when the launch wrote them) and the colours (palette: compare's)"""
     if out is not None:
-        compare(rt, pal_tree, out, ref, label)
+        compare(rt, pal_tree, out, ref, label, palette)
         assert (out["pos_steps"][:, 3] >= 0).all(), label
     _check(rgba, ref["rgba"], ref["hit"], label)
 

@@ -27,11 +27,16 @@ def gtree(torch_cuda, ref_tree):
     return ref_tree
 
 
-def compare(rt, tree, gpu_out, ref, label):
+def compare(rt, tree, gpu_out, ref, label, palette=None):
+    """palette: the tree's palette already decoded as (flags u32 array, colours u64 array), for callers that compare
+    many launches over a tree of tens of thousands of materials"""
     g = rt.decode_hits(gpu_out)
-    pal = tree.palette()
-    pf = np.array([p[0] for p in pal], np.uint32)
-    pc = np.array([p[1] for p in pal], np.uint64)
+    if palette is None:
+        pal = tree.palette()
+        pf = np.array([p[0] for p in pal], np.uint32)
+        pc = np.array([p[1] for p in pal], np.uint64)
+    else:
+        pf, pc = palette
     n = len(ref["hit"])
     assert len(g["hit"]) == n, label
     bad = np.nonzero((g["pos"] != ref["pos"]).any(1))[0]

@@ -48,8 +48,8 @@ def old64():
     return vol
 
 
-def _tree(rt, levels, vol, view=0):
-    return rt.Tree.volume_gpu(levels, np.array(vol, np.uint16), PAL, view=view)
+def _tree(rt, levels, vol, view=0, pal=PAL):
+    return rt.Tree.volume_gpu(levels, np.array(vol, np.uint16), pal, view=view)
 
 
 def _put(comp, new, origin):
@@ -65,10 +65,10 @@ def _kinds(tree):
     return n[:, 0], (n[:, 1] >> np.uint64(32)) & np.uint64(3), n[:, 1] >> np.uint64(48)
 
 
-def check_content(t, comp, view, origin, shape, seed=1):
-    """(a), (b), (e)"""
+def check_content(t, comp, view, origin, shape, seed=1, pal=PAL):
+    """(a), (b), (e); pal: the tree's palette"""
     E = comp.shape[0]
-    want = vc.in_view(comp, PAL, view)
+    want = vc.in_view(comp, pal, view)
     got = t.read_volume((0, 0, 0), (E, E, E)).cpu().numpy().view(np.uint16)
     assert np.array_equal(got, want), "(a) %d voxels differ" % int((got != want).sum())
     lo = [(o // 16) * 16 for o in origin]
@@ -99,14 +99,14 @@ def check_casts(rt, cuda, t, fresh, label, shift=(0.0, 0.0, 0.0), ao=False):
     return hits
 
 
-def check_all(rt, cuda, t, comp, view, origin, shape, label, levels=3, casts=True):
-    check_content(t, comp, view, origin, shape)
-    fresh = _tree(rt, levels, comp, view)
+def check_all(rt, cuda, t, comp, view, origin, shape, label, levels=3, casts=True, pal=PAL):
+    check_content(t, comp, view, origin, shape, pal=pal)
+    fresh = _tree(rt, levels, comp, view, pal)
     _same_ceilings(t, fresh, "(c) " + label)
     if casts and view == 0:
         check_casts(rt, cuda, t, fresh, label)
     elif casts:  # a full-view tree is walked as the scene of the shading pass: its primary, reflected and refracted rays
-        solid = _tree(rt, levels, comp, 0)
+        solid = _tree(rt, levels, comp, 0, pal)
         for ci, (org, d) in enumerate(CAMS):
             dn = rt.normalize(d)
             (ca, ha), (cb, hb) = (solid.shade_frame(org, dn, 64, 32, 300, scene=s, time=0.25, with_hits=True) for s in (t, fresh))

@@ -103,11 +103,13 @@ def voxel_puts(vol, origin):
     return [(int(a) + origin[0], int(b) + origin[1], int(c) + origin[2], int(i), None) for a, b, c, i in zip(x, y, z, vol[z, y, x])]
 
 
-def host_twin(rt, levels, vol, origin, view, table=TABLE):
+def host_twin(rt, levels, vol, origin, view, table=TABLE, world=None):
     """(host tree of `view`, its palette, the volume in that palette's ids): an rt.World filled with put_blocks over the
     non-zero voxels at level levels + 1, built; the volume remapped to the host palette by (flags, colour), so that both
-    builders number the materials alike by construction"""
-    w = rt.World(levels)
+    builders number the materials alike by construction.  world: an empty World to fill instead of a new one — one whose
+    palette already holds `table` entry for entry (palette_cases.world_with_palette) numbers the materials as the table
+    does, and the remap is the identity"""
+    w = rt.World(levels) if world is None else world
     z, y, x = np.nonzero(vol)
     ids = vol[z, y, x]
     flags = np.array([t[0] for t in table], np.uint32)
@@ -120,6 +122,8 @@ def host_twin(rt, levels, vol, origin, view, table=TABLE):
     remap = np.zeros(len(table), np.uint16)
     for i in range(1, len(table)):
         remap[i] = key.get((1 | table[i][0], table[i][1]), 0)
+    if world is not None:
+        assert len(pal) == len(table) and np.array_equal(remap[1:], np.arange(1, len(table))), "the world's palette is not the table"
     return h, pal, remap[vol]
 
 

@@ -30,7 +30,7 @@ extern "C" {
                              svo_wire_scatter / svo_exchange_wire.  Entry points added since keep the number and are
                              detected by symbol (dlsym / hasattr): svo_build_volume_gpu, svo_tree_read_volume,
                              svo_volume_classify_pass, svo_tree_patch_volume_gpu, svo_tree_garbage,
-                             svo_tree_patch_times */
+                             svo_tree_patch_times, svo_tree_compact_gpu, svo_tree_compact_times */
 
 enum {
     SVO_OK = 0,
@@ -197,7 +197,7 @@ int svo_volume_classify_pass(const svo_volume_desc* v, int32_t runs, float* ms);
    The device is synchronised on entry (the box may come from any stream, and records and ceilings are rewritten in
    place: svo_tree_sync's contract: call it between frames); the call is complete on return.
    Not done here: palette growth (ids are the tree's own palette), and compaction of superseded records
-   (svo_tree_garbage tells the caller when a rebuild, e.g. svo_tree_read_volume + svo_build_volume_gpu, pays). */
+   (svo_tree_garbage tells the caller when svo_tree_compact_gpu pays). */
 typedef struct {
     int32_t nx, ny, nz;        /* voxels[((int64)z * ny + y) * nx + x], as svo_volume_desc */
     int32_t origin[3];         /* world position of voxels[0]; origin >= 0, origin + n <= extent (no wrap) */
@@ -211,6 +211,31 @@ int svo_tree_garbage(const svo_tree* t, uint64_t* nodes, uint64_t* mats);
    its entry synchronisation: ms[0] the device passes (pyramid, count and write passes into scratch), ms[1] the commit to
    the arrays and the copy back to the host image, ms[2] the host's ceiling update (with the tree's top row) */
 int svo_tree_patch_times(const svo_tree* t, double ms[3]);
+/* Re-emit an uploaded tree, on its device, as the canonical linearisation of its own content: after the call the node
+   array, the material runs, nodes_per_level, n_bricks and n_mat_bytes equal, byte for byte, what svo_build_volume_gpu
+   emits for the same content under the same palette and view (for a tree that still follows an svo_world: what
+   svo_build_view emits for that world).  Uniform regions are K_SOLID at the highest level at which they are uniform,
+   empty regions clear their slot bit (no K_INTERIOR record with mask 0 but the lone root of an empty tree), a full
+   one-material brick is a K_SOLID child, a partial one K_BRICK | K_UNIFORM without a material run; svo_tree_garbage
+   reports (0, 0).  Only the tree is read — reachable records top down, their classes bottom up, then the builders' own
+   emitter — so the cost follows the tree's size, not the extent's volume.
+   The device arrays are new allocations with the slack of a fresh upload and the old ones are freed (device_bytes is
+   that of a freshly built tree of the same content); the host image mirrors them.  Unchanged: the palette (ids are not
+   renumbered, unused entries stay), view and levels; the content, hence the column ceilings, which are kept and not
+   recomputed; the guard-trip counter, the AO plan and the frame schedules; whether svo_tree_update accepts the tree (a
+   world-built tree edited only through svo_tree_update still follows its world afterwards; one patched by
+   svo_tree_patch_volume_gpu still gets SVO_ESTATE).
+   SVO_EINVAL: NULL tree; SVO_ESTATE: the tree is not uploaded, or has host edits not yet synced (svo_tree_sync);
+   SVO_ENOMEM: no scratch — everything is emitted beside the old arrays and swapped in at the end, so the tree is then
+   untouched on host and device.  Arguments are checked before the first HIP call.  The device is synchronised on entry
+   (the arrays are replaced: call it between frames); the call is complete on return.  Trees of any size (every index
+   is widened to 64 bits before it addresses memory); trees of one level and lone roots return SVO_OK.  The caller
+   decides when: svo_tree_patch_volume_gpu never compacts by itself. */
+int svo_tree_compact_gpu(svo_tree* t);
+/* diagnostics (tools/volume_compact_timing.py): host-clock milliseconds of the tree's last svo_tree_compact_gpu, after its
+   entry synchronisation: ms[0] the device passes (reach, classes, emission into the new arrays), ms[1] the copy back
+   to the host image and the swap, ms[2] the release of the scratch allocations and of the old host image */
+int svo_tree_compact_times(const svo_tree* t, double ms[3]);
 int svo_tree_get_info(const svo_tree* t, svo_tree_info* out);
 /* palette entry `id` (id 0 = empty block) */
 int svo_tree_palette(const svo_tree* t, uint32_t id, svo_block* out);

@@ -162,7 +162,7 @@ ABI_SYMBOLS = (
     "svo_tree_save", "svo_tree_load", "svo_wire_bytes", "svo_cast_wire", "svo_wire_scatter", "svo_exchange_wire", "svo_tree_ceilings",
     "svo_tree_guard_trips", "svo_ceiling_layout", "svo_tree_device_ceilings", "svo_tree_device_ceiling_quads", "svo_tree_schedule", "svo_cast_ray_from_cam_async",
     "svo_build_id", "svo_build_volume_gpu", "svo_tree_read_volume", "svo_volume_classify_pass",
-    "svo_tree_patch_volume_gpu", "svo_tree_garbage", "svo_tree_patch_times",
+    "svo_tree_patch_volume_gpu", "svo_tree_garbage", "svo_tree_patch_times", "svo_tree_compact_gpu", "svo_tree_compact_times",
 )
 
 
@@ -246,7 +246,8 @@ def lib():
                      ("svo_volume_classify_pass", [C.POINTER(VolumeDesc), i32, C.POINTER(f32)]),
                      ("svo_tree_patch_volume_gpu", [vp, C.POINTER(VolumeBox)]),
                      ("svo_tree_garbage", [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
-                     ("svo_tree_patch_times", [vp, C.POINTER(C.c_double)])):
+                     ("svo_tree_patch_times", [vp, C.POINTER(C.c_double)]),
+                     ("svo_tree_compact_gpu", [vp]), ("svo_tree_compact_times", [vp, C.POINTER(C.c_double)])):
         if hasattr(L, name):
             getattr(L, name).argtypes = at
     L.svo_build_terrain.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
@@ -579,7 +580,7 @@ class Tree:
 
     def garbage(self):
         """svo_tree_garbage: (node records, material entries) superseded by update() / patch_volume() since the last
-        full build: when they outweigh the tree, a rebuild pays"""
+        full build or compact(): when they outweigh the tree, compact() pays"""
         n, m = C.c_uint64(), C.c_uint64()
         _check(lib().svo_tree_garbage(self._h, C.byref(n), C.byref(m)), "svo_tree_garbage")
         return n.value, m.value
@@ -588,6 +589,20 @@ class Tree:
         """svo_tree_patch_times: host-clock ms of the last patch_volume() — (device passes, commit + host image, ceilings)"""
         ms = (C.c_double * 3)()
         _check(lib().svo_tree_patch_times(self._h, ms), "svo_tree_patch_times")
+        return tuple(ms)
+
+    def compact(self):
+        """svo_tree_compact_gpu: re-emit this (uploaded) tree, on its device, as the canonical linearisation of its own
+        content — what volume_gpu() builds from the same voxels, byte for byte.  Superseded records go (garbage() is
+        (0, 0) afterwards), regions that edits made uniform or empty collapse again, and the arrays are sized as after a
+        fresh build; content, palette, view, ceilings and schedules stay.  The call is complete on return."""
+        _check(lib().svo_tree_compact_gpu(self._h), "svo_tree_compact_gpu")
+        return self
+
+    def compact_times(self):
+        """svo_tree_compact_times: host-clock ms of the last compact() — (device passes, host image + swap, release of the scratch)"""
+        ms = (C.c_double * 3)()
+        _check(lib().svo_tree_compact_times(self._h, ms), "svo_tree_compact_times")
         return tuple(ms)
 
     def read_volume(self, origin, shape, out=None, stream=None):

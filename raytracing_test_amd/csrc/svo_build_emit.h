@@ -1,5 +1,5 @@
 // svo_build_emit.h — the level-synchronous breadth-first emitter of the on-device builders (svo_build.hip: terrain
-// columns; svo_build_volume.hip: dense voxel volumes), generic over its source.  A source S is passed to the kernels
+// columns; svo_build_volume.hip: dense voxel volumes; svo_compact.hip: a resident tree), generic over its source.  A source S is passed to the kernels
 // by value and answers two questions on the device:
 //   uint32_t S::classify(x0, y0, z0, s, k)   class of the aligned region [x0, x0+s)^3, s = 4^k, k >= 1:
 //                                            G_EMPTY, a palette id (the whole region that material), or G_MIXED
@@ -7,7 +7,8 @@
 // One wavefront per region, one lane per child slot (or per voxel at the brick level): ballots give the child mask,
 // the MIXED children and the stored voxels; exclusive scans over the regions (hipCUB) place every child block and
 // material run; a second pass writes them.  The output is the host's canonical linearisation (svo_linearise.cpp
-// svo_build_view) byte for byte, left in HBM and adopted as the tree's uploaded copy.
+// svo_build_view) byte for byte, left in HBM (emit_arrays); the builders adopt it as a new tree's uploaded copy
+// (emit_tree), the compaction swaps it in under a tree that keeps the rest of its residency.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -164,11 +165,21 @@ int for_region_chunks(int64_t n, F&& launch) {
     return SVO_OK;
 }
 
-// Emit the tree of source T into t (levels, view and palette already set) and leave it uploaded to `device`.
+// What an emission leaves in HBM: the canonical arrays in allocations with slack for edits (the rule of svo_upload), still
+// owned by the emitter's pool, and the statistics a tree carries
+struct Emitted {
+    Node* nodes = nullptr;
+    uint16_t* mats = nullptr;
+    uint64_t n_nodes = 0, node_cap = 0, n_mats = 0, mat_cap = 0;
+    uint64_t nodes_per_level[8] = {0};
+    uint64_t n_bricks = 0;
+};
+
+// Emit the tree of source T (`levels` deep) into new device arrays: *e.  Nothing but the pool is touched.
 // root_class: the class of the whole extent — G_MIXED descends; G_EMPTY is the lone record {0, 0, K_INTERIOR}; a
 // palette id is a lone K_SOLID root (svo_build_view's two roots without children).  `who` prefixes error messages.
 template <class S>
-int emit_tree(const S& T, int32_t levels, uint32_t root_class, svo_tree* t, Pool& pool, int32_t device, const char* who) {
+int emit_arrays(const S& T, int32_t levels, uint32_t root_class, Pool& pool, const char* who, Emitted* e) {
     // node array: grown per level (capacity doubling, device copies)
     uint64_t cap = 1 << 16, used = 1;
     Node* nodes;
@@ -198,7 +209,7 @@ int emit_tree(const S& T, int32_t levels, uint32_t root_class, svo_tree* t, Pool
     if (rc) return rc;
     HIP_TRY(hipMemcpy(cur, &root, sizeof(Region), hipMemcpyHostToDevice), SVO_EDEVICE);
     int64_t ncur = 1;
-    t->nodes_per_level[0] = 1;
+    e->nodes_per_level[0] = 1;
     Node root_rec{0, 0, K_INTERIOR};
     if (root_class != G_MIXED) {  // a root without children: nothing to descend into
         if (root_class != G_EMPTY) root_rec = Node{~0ull, 0u, K_SOLID | (root_class << 16)};
@@ -226,7 +237,7 @@ int emit_tree(const S& T, int32_t levels, uint32_t root_class, svo_tree* t, Pool
                 hipLaunchKernelGGL(k_brick_write<S>, g, dim3(256), 0, nullptr, T, cur, r0, ncur, moff, nodes, mats);
             });
             if (rc) return rc;
-            t->n_bricks = (uint64_t)ncur;
+            e->n_bricks = (uint64_t)ncur;
             break;
         }
         uint32_t *nkid, *nmix;
@@ -253,14 +264,14 @@ int emit_tree(const S& T, int32_t levels, uint32_t root_class, svo_tree* t, Pool
             hipLaunchKernelGGL(k_write<S>, g, dim3(256), 0, nullptr, T, cur, r0, ncur, cs, levels - d - 1, koff, moff, used, nodes, next);
         });
         if (rc) return rc;
-        t->nodes_per_level[d + 1] = nk;
+        e->nodes_per_level[d + 1] = nk;
         used += nk;
         cur = next;
         ncur = (int64_t)nm;
     }
     HIP_TRY(hipDeviceSynchronize(), SVO_EDEVICE);
     for (void* x : tmp) (void)hipFree(x);
-    // host image + adoption of the device arrays (with slack for edits)
+    // the arrays with slack for edits
     const uint64_t ncap = std::min<uint64_t>(used + used / 8 + 65536, 1ull << 32), mcap = std::min<uint64_t>(n_mats + n_mats / 8 + 65536, 1ull << 32);
     Node* dn;
     uint16_t* dm;
@@ -269,18 +280,36 @@ int emit_tree(const S& T, int32_t levels, uint32_t root_class, svo_tree* t, Pool
     if (rc) return rc;
     HIP_TRY(hipMemcpy(dn, nodes, used * sizeof(Node), hipMemcpyDeviceToDevice), SVO_EDEVICE);
     if (n_mats) HIP_TRY(hipMemcpy(dm, mats, n_mats * sizeof(uint16_t), hipMemcpyDeviceToDevice), SVO_EDEVICE);
-    t->nodes.reserve(ncap);  // (the host image with the device arrays' slack: appended tails do not move it)
-    t->mats.reserve(mcap);
-    t->nodes.resize(used);
-    t->mats.resize(n_mats);
-    HIP_TRY(hipMemcpy(t->nodes.data(), dn, used * sizeof(Node), hipMemcpyDeviceToHost), SVO_EDEVICE);
-    if (n_mats) HIP_TRY(hipMemcpy(t->mats.data(), dm, n_mats * sizeof(uint16_t), hipMemcpyDeviceToHost), SVO_EDEVICE);
-    pool.release(dn);
-    pool.release(dm);
-    rc = adopt_device(t, device, dn, ncap, dm, mcap);
+    e->nodes = dn;
+    e->mats = dm;
+    e->n_nodes = used;
+    e->node_cap = ncap;
+    e->n_mats = n_mats;
+    e->mat_cap = mcap;
+    return SVO_OK;
+}
+
+// Emit the tree of source T into t (levels, view and palette already set) and leave it uploaded to `device`: the host
+// image is copied back and the arrays are adopted, which computes the rest of the residency (ceilings included) anew.
+template <class S>
+int emit_tree(const S& T, int32_t levels, uint32_t root_class, svo_tree* t, Pool& pool, int32_t device, const char* who) {
+    Emitted e;
+    int rc = emit_arrays(T, levels, root_class, pool, who, &e);
+    if (rc) return rc;
+    for (int i = 0; i < 8; i++) t->nodes_per_level[i] = e.nodes_per_level[i];
+    t->n_bricks = e.n_bricks;
+    t->nodes.reserve(e.node_cap);  // (the host image with the device arrays' slack: appended tails do not move it)
+    t->mats.reserve(e.mat_cap);
+    t->nodes.resize(e.n_nodes);
+    t->mats.resize(e.n_mats);
+    HIP_TRY(hipMemcpy(t->nodes.data(), e.nodes, e.n_nodes * sizeof(Node), hipMemcpyDeviceToHost), SVO_EDEVICE);
+    if (e.n_mats) HIP_TRY(hipMemcpy(t->mats.data(), e.mats, e.n_mats * sizeof(uint16_t), hipMemcpyDeviceToHost), SVO_EDEVICE);
+    pool.release(e.nodes);
+    pool.release(e.mats);
+    rc = adopt_device(t, device, e.nodes, e.node_cap, e.mats, e.mat_cap);
     if (rc) {
-        (void)hipFree(dn);
-        (void)hipFree(dm);
+        (void)hipFree(e.nodes);
+        (void)hipFree(e.mats);
         return rc;
     }
     return SVO_OK;

@@ -88,6 +88,9 @@ struct svo_tree {
     // host-clock milliseconds of the last patch (svo_tree_patch_times): the device passes up to the totals, the commit and
     // the copy back to the host image, the ceiling update with tree_top_y
     double patch_ms[3] = {0.0, 0.0, 0.0};
+    // host-clock milliseconds of the last compaction (svo_tree_compact_times): the device passes up to the new arrays, the
+    // copy back to the host image with the swap, the release of the scratch and of the old arrays
+    double compact_ms[3] = {0.0, 0.0, 0.0};
     uint64_t dev_node_cap = 0, dev_mat_cap = 0, dev_pal_n = 0;  // device allocations (elements)
     // highest voxel row holding a stored voxel (tree_top_y; -1: empty tree), cached until an edit
     mutable int32_t top_y = -1;

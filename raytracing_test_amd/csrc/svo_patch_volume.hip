@@ -30,6 +30,7 @@
 #include "svo_hip.h"
 #include "svo_internal.h"
 #include "svo_plan.h"
+#include "svo_tree_descent.h"
 #include "svo_volume_pyramid.h"
 
 using namespace svo;
@@ -64,27 +65,7 @@ __device__ __forceinline__ uint32_t relation(const DevPatch& P, int32_t x, int32
     return out ? REL_OUT : (in ? REL_IN : REL_CUT);
 }
 
-// svo_tree_get_block's descent over the resident arrays
-__device__ uint32_t old_voxel(const DevPatch& P, uint32_t wx, uint32_t wy, uint32_t wz) {
-    uint64_t ni = 0;
-    for (int d = 0; d < P.levels; d++) {
-        const Node n = P.nodes[ni];
-        const uint32_t kind = node_kind(n.info);
-        if (kind == K_SOLID) return node_material(n.info);
-        if (kind == K_BRICK) {
-            const uint32_t v = ((wz & 3u) << 4) | ((wy & 3u) << 2) | (wx & 3u);
-            if (!((n.mask >> v) & 1ull)) return G_EMPTY;
-            return (n.info & K_UNIFORM) ? node_material(n.info) : P.mats[(uint64_t)n.ref + (uint64_t)__popcll(n.mask & ((1ull << v) - 1ull))];
-        }
-        const uint32_t sh = (uint32_t)(2 * (P.levels - 1 - d));
-        const uint32_t sl = (((wz >> sh) & 3u) << 4) | (((wy >> sh) & 3u) << 2) | ((wx >> sh) & 3u);
-        if (!((n.mask >> sl) & 1ull)) return G_EMPTY;
-        ni = (uint64_t)n.ref + (uint64_t)__popcll(n.mask & ((1ull << sl) - 1ull));
-    }
-    return G_EMPTY;
-}
-
-// the composite: the box's voxel (after the view filter) inside the box, the old tree's outside
+// the composite: the box's voxel (after the view filter) inside the box, the old tree's outside (svo_tree_descent.h)
 __device__ __forceinline__ uint32_t comp_voxel(const DevPatch& P, int32_t x, int32_t y, int32_t z) {
     const bool in = x >= P.b0[0] && x < P.b1[0] && y >= P.b0[1] && y < P.b1[1] && z >= P.b0[2] && z < P.b1[2];
     return in ? P.V.voxel(x, y, z) : old_voxel(P, (uint32_t)x, (uint32_t)y, (uint32_t)z);

@@ -30,7 +30,8 @@ extern "C" {
                              svo_wire_scatter / svo_exchange_wire.  Entry points added since keep the number and are
                              detected by symbol (dlsym / hasattr): svo_build_volume_gpu, svo_tree_read_volume,
                              svo_volume_classify_pass, svo_tree_patch_volume_gpu, svo_tree_garbage,
-                             svo_tree_patch_times, svo_tree_compact_gpu, svo_tree_compact_times */
+                             svo_tree_patch_times, svo_tree_compact_gpu, svo_tree_compact_times,
+                             svo_build_points_gpu, svo_tree_get_blocks_gpu */
 
 enum {
     SVO_OK = 0,
@@ -176,6 +177,48 @@ int svo_tree_read_volume(const svo_tree* t, const int32_t origin[3], int32_t nx,
 /* diagnostics (tools/volume_build_timing.py): svo_build_volume_gpu's first pass alone — the level-1 classification,
    which reads the whole volume — run `runs` times into scratch, each timed by HIP events: ms[0 .. runs-1] */
 int svo_volume_classify_pass(const svo_volume_desc* v, int32_t runs, float* ms);
+/* A tree from a sparse list of voxels already in HBM (a voxelised mesh, a point cloud, a particle or fluid front,
+   procedural scatter): the route to arbitrary content in worlds too large for a dense volume (levels 6 and 7).  The cost
+   follows the number of points, never the extent's volume.  The points are applied in list order, as svo_put_blocks
+   applies its blocks: when a voxel is listed more than once its last entry decides, and a last entry of id 0 leaves the
+   voxel empty.  After that resolution an id is stored when the view holds its palette entry (svo_build_volume_gpu's
+   rule: a LIQUID entry written last over a solid one gives an empty voxel in SVO_VIEW_SOLID, a liquid one in
+   SVO_VIEW_ALL).  The output is the canonical linearisation: nodes, material runs, nodes_per_level, n_bricks,
+   n_mat_bytes and palette equal, byte for byte, what svo_build_view emits for a world holding that content under the
+   same palette ids, and what svo_build_volume_gpu emits for a dense volume of it.  n == 0 builds the empty tree, the
+   lone record {0, 0, K_INTERIOR}; xyz and ids may then be NULL.
+   One lane per point computes a 64-bit key (6 bits per level, the child slots from the root down) and checks the
+   point; a stable radix sort of (key, id) puts every voxel's entries next to each other in list order; the stored
+   voxels are compacted, and each level above holds the occupied 4^k cells with their classes (an id when all 64
+   children carry it, else mixed), which the level-synchronous emitter of the other GPU builders searches.
+   Scratch in HBM, freed on return: 24 B per point (two (key, id) pairs for the sort and a flag word), 10 B per stored
+   voxel, 14 B per occupied cell of each of the `levels` levels above (a level never has more cells than the one below
+   it, and 1/64 of them where the content is dense: at most 34 + 14 * levels B per point in all), hipCUB's sort and scan
+   temporaries, and the emitter's own scratch per emitted region.
+   SVO_EINVAL: NULL p or out, NULL xyz or ids with n > 0, NULL palette, levels outside 2..7, n < 0, an unknown view,
+   palette[0] not the empty block; SVO_ERANGE: n_palette outside 1..65535, n > 2^31 - 1 — all checked before the first
+   HIP call — and, found on the device by the first pass, an id >= n_palette or a coordinate outside [0, 4^levels):
+   nothing is emitted, *out is untouched and the message says which of the two it was; SVO_ENOMEM: no scratch.  The
+   device is synchronised on entry (the list may come from any stream); the build runs on the null stream.  The tree
+   comes back uploaded to `device` with its host image, ceilings included.  It has no svo_world behind it:
+   svo_tree_update returns SVO_ESTATE on it; svo_tree_patch_volume_gpu and svo_tree_compact_gpu accept it. */
+typedef struct {
+    int32_t levels;              /* extent 4^levels per axis; 2..7 */
+    int64_t n;                   /* points; 0 .. 2^31 - 1 */
+    const int32_t* xyz;          /* DEVICE pointer on `device`: 3 x int32 per point (svo_get_blocks' layout); 0 <= c < 4^levels (no wrap) */
+    const uint16_t* ids;         /* DEVICE pointer on `device`: palette id per point, 0 = empty */
+    const svo_block* palette;    /* HOST: n_palette entries; entry 0 must be the empty block (as svo_volume_desc) */
+    uint32_t n_palette;          /* 1..65535 */
+    int32_t view;                /* SVO_VIEW_SOLID / SVO_VIEW_ALL */
+    int32_t device;
+} svo_points_desc;
+int svo_build_points_gpu(const svo_points_desc* p, svo_tree** out);
+/* the palette id the tree stores (its view) at each of n positions given in HBM (xyz = 3 x int32 each), written to the
+   device buffer ids; coordinates wrap modulo the extent as svo_tree_get_blocks' and svo_tree_read_volume's do.  One lane
+   per position descends the resident arrays (every index widened to 64 bits); asynchronous on hip_stream.  Any uploaded
+   tree, however built, patched or not.  SVO_EINVAL: NULL tree, NULL buffers with n > 0, n < 0; SVO_ESTATE: the tree is
+   not uploaded; n == 0 returns SVO_OK without a launch */
+int svo_tree_get_blocks_gpu(const svo_tree* t, const int32_t* xyz, int64_t n, uint16_t* ids, void* hip_stream);
 /* Patch a resident tree from a dense box of voxels in HBM, on the device: after the call the tree's content inside the
    box is exactly `voxels` (ids the tree's view does not hold are stored empty, as in svo_build_volume_gpu); everything
    outside the box is as before.  Any uploaded tree (volume-, terrain- or world-built), either view, any size (nodes are

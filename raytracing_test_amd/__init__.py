@@ -132,6 +132,13 @@ class VolumeBox(C.Structure):
     _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("origin", C.c_int32 * 3), ("voxels", C.c_void_p)]
 
 
+class PointsDesc(C.Structure):
+    """svo_points_desc: a sparse list of n voxels (x, y, z) with their palette ids in HBM, in a 4^levels world"""
+
+    _fields_ = [("levels", C.c_int32), ("n", C.c_int64), ("xyz", C.c_void_p), ("ids", C.c_void_p), ("palette", C.POINTER(Block)),
+                ("n_palette", C.c_uint32), ("view", C.c_int32), ("device", C.c_int32)]
+
+
 class Hits(C.Structure):
     _fields_ = [("pos_steps", C.c_void_p), ("t", C.c_void_p), ("info", C.c_void_p), ("ao", C.c_void_p)]
 
@@ -163,6 +170,7 @@ ABI_SYMBOLS = (
     "svo_tree_guard_trips", "svo_ceiling_layout", "svo_tree_device_ceilings", "svo_tree_device_ceiling_quads", "svo_tree_schedule", "svo_cast_ray_from_cam_async",
     "svo_build_id", "svo_build_volume_gpu", "svo_tree_read_volume", "svo_volume_classify_pass",
     "svo_tree_patch_volume_gpu", "svo_tree_garbage", "svo_tree_patch_times", "svo_tree_compact_gpu", "svo_tree_compact_times",
+    "svo_build_points_gpu", "svo_tree_get_blocks_gpu",
 )
 
 
@@ -247,7 +255,9 @@ def lib():
                      ("svo_tree_patch_volume_gpu", [vp, C.POINTER(VolumeBox)]),
                      ("svo_tree_garbage", [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
                      ("svo_tree_patch_times", [vp, C.POINTER(C.c_double)]),
-                     ("svo_tree_compact_gpu", [vp]), ("svo_tree_compact_times", [vp, C.POINTER(C.c_double)])):
+                     ("svo_tree_compact_gpu", [vp]), ("svo_tree_compact_times", [vp, C.POINTER(C.c_double)]),
+                     ("svo_build_points_gpu", [C.POINTER(PointsDesc), C.POINTER(vp)]),
+                     ("svo_tree_get_blocks_gpu", [vp, vp, C.c_int64, vp, vp])):
         if hasattr(L, name):
             getattr(L, name).argtypes = at
     L.svo_build_terrain.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
@@ -556,6 +566,94 @@ class Tree:
         _check(lib().svo_build_volume_gpu(C.byref(d), C.byref(h)), "svo_build_volume_gpu")
         del keep
         return cls(h)
+
+    @staticmethod
+    def _device_points(xyz, ids, device):
+        """the (n, 3) int32 position tensor and the n-long id tensor on cuda:`device` that a point-list argument stands for
+        (numpy arrays are uploaded), validated: ValueError for a wrong dtype, shape, length or device or a non-contiguous
+        tensor.  ids=None: positions alone"""
+        torch = _torch()
+        host = [False, False]  # numpy arguments: checked as host tensors, uploaded once everything has passed
+        if isinstance(xyz, np.ndarray):
+            if xyz.dtype != np.int32 or xyz.ndim != 2 or xyz.shape[1] != 3:
+                raise ValueError("xyz: a numpy point list must be an int32 array of shape (n, 3)")
+            xyz, host[0] = torch.from_numpy(np.ascontiguousarray(xyz)), True
+        if isinstance(ids, np.ndarray):
+            if ids.dtype not in (np.uint16, np.int16) or ids.ndim != 1:
+                raise ValueError("ids: a numpy id list must be a uint16 or int16 array of shape (n,)")
+            ids, host[1] = torch.from_numpy(np.ascontiguousarray(ids).view(np.int16)), True
+        if not isinstance(xyz, torch.Tensor):
+            raise ValueError("xyz: a torch tensor or a numpy int32 array")
+        if xyz.dtype != torch.int32:
+            raise ValueError("xyz: dtype must be torch.int32, not %s" % xyz.dtype)
+        if xyz.dim() != 2 or xyz.shape[1] != 3:
+            raise ValueError("xyz: shape must be (n, 3), not %s" % (tuple(xyz.shape),))
+        if not xyz.is_contiguous():
+            raise ValueError("xyz: the tensor must be contiguous")
+        if ids is not None:
+            if not isinstance(ids, torch.Tensor):
+                raise ValueError("ids: a torch tensor or a numpy uint16 array")
+            if ids.dtype not in (torch.uint16, torch.int16):
+                raise ValueError("ids: dtype must be torch.uint16 or torch.int16, not %s" % ids.dtype)
+            if ids.dim() != 1:
+                raise ValueError("ids: shape must be (n,), not %s" % (tuple(ids.shape),))
+            if ids.shape[0] != xyz.shape[0]:
+                raise ValueError("ids: length %d does not match the %d points of xyz" % (ids.shape[0], xyz.shape[0]))
+            if not ids.is_contiguous():
+                raise ValueError("ids: the tensor must be contiguous")
+        out = []
+        for name, t, h in (("xyz", xyz, host[0]), ("ids", ids, host[1])):
+            if t is not None and not h and (not t.is_cuda or t.device.index != device):
+                raise ValueError("%s: the tensor must live on cuda:%d, not %s" % (name, device, t.device))
+            out.append(t.to(torch.device("cuda", device)) if h else t)
+        return out[0], out[1]
+
+    @classmethod
+    def points_gpu(cls, levels, xyz, ids, palette, view=VIEW_SOLID, device=0):
+        """svo_build_points_gpu: the canonical tree of a sparse list of voxels, built in HBM and returned uploaded to
+        `device`; the cost follows the number of points, not the extent (levels up to 7).  xyz: a contiguous CUDA int32
+        tensor (n, 3) of positions within the extent, or a numpy int32 array of that shape (uploaded through torch); ids:
+        n palette ids, torch.uint16 / torch.int16 (the bits are the ids) or numpy; palette: [(flags, color, metadata)],
+        entry 0 the empty block.  The points are applied in order: a voxel's last entry decides, id 0 erases.  Such a
+        tree has no World behind it (update() fails): it is changed in HBM by patch_volume()."""
+        xyz, ids = cls._device_points(xyz, ids, device)
+        pal = (Block * max(1, len(palette)))()
+        for i, (f, c, m) in enumerate(palette):
+            pal[i] = Block(int(f), int(c), float(m))
+        d = PointsDesc()
+        d.levels = levels
+        d.n = int(xyz.shape[0])
+        d.xyz = xyz.data_ptr() if d.n else None
+        d.ids = ids.data_ptr() if d.n else None
+        d.palette = pal
+        d.n_palette = len(palette)
+        d.view = view
+        d.device = device
+        h = C.c_void_p()
+        _check(lib().svo_build_points_gpu(C.byref(d), C.byref(h)), "svo_build_points_gpu")
+        del xyz, ids
+        return cls(h)
+
+    def get_blocks_gpu(self, points, out=None, stream=None):
+        """svo_tree_get_blocks_gpu: the palette ids this (uploaded) tree stores at `points` — a contiguous CUDA int32 tensor
+        (n, 3) on the tree's device, or a numpy int32 array of that shape (uploaded through torch) — as an int16 CUDA
+        tensor of n ids (the bits are the ids; coordinates wrap modulo the extent); asynchronous on `stream`"""
+        torch = _torch()
+        dev = self.info().device
+        if dev < 0:
+            raise SvoError("svo_tree_get_blocks_gpu failed (-4): tree not uploaded (svo_upload)")
+        points, _ = self._device_points(points, None, dev)
+        n = int(points.shape[0])
+        if out is None:
+            out = torch.empty((n,), dtype=torch.int16, device=torch.device("cuda", dev))
+        elif (tuple(out.shape) != (n,) or out.dtype not in (torch.int16, torch.uint16) or not out.is_cuda or out.device.index != dev
+              or not out.is_contiguous()):
+            raise ValueError("out: a contiguous int16 CUDA tensor of shape (n,) on the tree's device")
+        s = getattr(stream, "cuda_stream", stream)
+        _check(lib().svo_tree_get_blocks_gpu(self._h, C.c_void_p(points.data_ptr()) if n else None, n,
+                                             C.c_void_p(out.data_ptr()) if n else None, C.c_void_p(s) if s else None),
+               "svo_tree_get_blocks_gpu")
+        return out
 
     def patch_volume(self, voxels, origin):
         """svo_tree_patch_volume_gpu: replace this (uploaded) tree's content inside a box by `voxels`, on the device.

@@ -1,5 +1,6 @@
 // svo_build_emit.h — the level-synchronous breadth-first emitter of the on-device builders (svo_build.hip: terrain
-// columns; svo_build_volume.hip: dense voxel volumes; svo_compact.hip: a resident tree), generic over its source.  A source S is passed to the kernels
+// columns; svo_build_volume.hip: dense voxel volumes; svo_build_points.hip: sparse voxel lists; svo_compact.hip: a
+// resident tree), generic over its source.  A source S is passed to the kernels
 // by value and answers two questions on the device:
 //   uint32_t S::classify(x0, y0, z0, s, k)   class of the aligned region [x0, x0+s)^3, s = 4^k, k >= 1:
 //                                            G_EMPTY, a palette id (the whole region that material), or G_MIXED

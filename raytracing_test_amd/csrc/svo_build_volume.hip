@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/svo_rt.h"
+#include "svo_build_args.h"
 #include "svo_build_emit.h"
 #include "svo_hip.h"
 #include "svo_internal.h"
@@ -67,20 +68,7 @@ int check_desc(const svo_volume_desc* v, const char* who) {
     const int32_t n[3] = {v->nx, v->ny, v->nz};
     for (int a = 0; a < 3; a++)
         if (v->origin[a] < 0 || (int64_t)v->origin[a] + n[a] > E) SVO_FAIL(SVO_EINVAL, w + ": the box must lie within the extent (no wrap)");
-    if (v->view != SVO_VIEW_SOLID && v->view != SVO_VIEW_ALL) SVO_FAIL(SVO_EINVAL, w + ": unknown view");
-    if (v->n_palette < 1 || v->n_palette > 65535) SVO_FAIL(SVO_ERANGE, w + ": n_palette must be in [1, 65535]");
-    if (v->palette[0].flags != 0 || v->palette[0].color != ~0ull || v->palette[0].metadata != 0.0f)
-        SVO_FAIL(SVO_EINVAL, w + ": palette[0] must be the empty block {0, ~0, 0}");
-    return SVO_OK;
-}
-
-int open_device(int32_t device, const char* who) {
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev), SVO_EDEVICE);
-    if (device < 0 || device >= ndev) SVO_FAIL(SVO_EDEVICE, std::string(who) + ": no such HIP device");
-    HIP_TRY(hipSetDevice(device), SVO_EDEVICE);
-    // the volume may have been produced on another stream; the build then runs on the null stream
-    HIP_TRY(hipDeviceSynchronize(), SVO_EDEVICE);
+    if (int rc = check_view_palette(v->view, v->palette, v->n_palette, w)) return rc;
     return SVO_OK;
 }
 

@@ -85,6 +85,8 @@ struct svo_tree {
     // svo_tree_patch_volume_gpu has changed the tree: it no longer mirrors the svo_world it was built from, and
     // svo_tree_update refuses it
     bool volume_patched = false;
+    // built by svo_build_points_gpu: no svo_world holds its content, and svo_tree_update refuses it
+    bool no_world = false;
     // host-clock milliseconds of the last patch (svo_tree_patch_times): the device passes up to the totals, the commit and
     // the copy back to the host image, the ceiling update with tree_top_y
     double patch_ms[3] = {0.0, 0.0, 0.0};

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/svo_rt.h"
+#include "svo_build_args.h"
 #include "svo_build_emit.h"
 #include "svo_hip.h"
 #include "svo_internal.h"
@@ -182,8 +183,8 @@ __global__ void k_vol_fold(const uint16_t* child, int32_t clx, int32_t cly, int3
     parent[i] = (uint16_t)f;
 }
 
-// the desc as the kernels see it: the stored palette (flags 1 | flags, as putBlock stores them), the in-view bit table
-// in HBM, the geometry of the class pyramid.  `all` = every id but 0 is in view (the table need not be consulted).
+// the desc as the kernels see it: the stored palette and the in-view bit table in HBM (svo_build_args.h view_table),
+// the geometry of the class pyramid.  `all` = every id but 0 is in view (the table need not be consulted).
 inline int prepare(const svo_volume_desc* v, Pool& pool, DevVolume& V, std::vector<Material>& pal, bool& all) {
     memset(&V, 0, sizeof(V));
     V.vox = v->voxels;
@@ -191,20 +192,8 @@ inline int prepare(const svo_volume_desc* v, Pool& pool, DevVolume& V, std::vect
     V.ny = v->ny;
     V.nz = v->nz;
     V.n_pal = v->n_palette;
-    pal.clear();
-    pal.push_back(Material{0, ~0ull, 0.0f});
-    for (uint32_t i = 1; i < v->n_palette; i++) pal.push_back(Material{1u | v->palette[i].flags, v->palette[i].color, v->palette[i].metadata});
-    std::vector<uint32_t> bits((v->n_palette + 31u) / 32u, 0u);
-    all = true;
-    for (uint32_t i = 1; i < v->n_palette; i++) {
-        if (material_in_view(pal[i], v->view)) bits[i >> 5] |= 1u << (i & 31u);
-        else all = false;
-    }
-    uint32_t* dbits;
-    int rc = pool.alloc(&dbits, bits.size());
+    int rc = view_table(v->palette, v->n_palette, v->view, pool, pal, &V.in_view, all);
     if (rc) return rc;
-    HIP_TRY(hipMemcpy(dbits, bits.data(), bits.size() * 4, hipMemcpyHostToDevice), SVO_EDEVICE);
-    V.in_view = dbits;
     const int32_t n[3] = {v->nx, v->ny, v->nz};
     for (int a = 0; a < 3; a++) V.o[a] = v->origin[a];
     for (int k = 1; k <= v->levels; k++)

@@ -31,7 +31,8 @@ extern "C" {
                              detected by symbol (dlsym / hasattr): svo_build_volume_gpu, svo_tree_read_volume,
                              svo_volume_classify_pass, svo_tree_patch_volume_gpu, svo_tree_garbage,
                              svo_tree_patch_times, svo_tree_compact_gpu, svo_tree_compact_times,
-                             svo_build_points_gpu, svo_tree_get_blocks_gpu */
+                             svo_build_points_gpu, svo_tree_get_blocks_gpu,
+                             svo_tree_patch_points_gpu */
 
 enum {
     SVO_OK = 0,
@@ -201,7 +202,8 @@ int svo_volume_classify_pass(const svo_volume_desc* v, int32_t runs, float* ms);
    nothing is emitted, *out is untouched and the message says which of the two it was; SVO_ENOMEM: no scratch.  The
    device is synchronised on entry (the list may come from any stream); the build runs on the null stream.  The tree
    comes back uploaded to `device` with its host image, ceilings included.  It has no svo_world behind it:
-   svo_tree_update returns SVO_ESTATE on it; svo_tree_patch_volume_gpu and svo_tree_compact_gpu accept it. */
+   svo_tree_update returns SVO_ESTATE on it; svo_tree_patch_volume_gpu, svo_tree_patch_points_gpu and
+   svo_tree_compact_gpu accept it. */
 typedef struct {
     int32_t levels;              /* extent 4^levels per axis; 2..7 */
     int64_t n;                   /* points; 0 .. 2^31 - 1 */
@@ -247,12 +249,45 @@ typedef struct {
     const uint16_t* voxels;    /* DEVICE pointer on the tree's device: ids of the tree's own palette, 0 = empty */
 } svo_volume_box;
 int svo_tree_patch_volume_gpu(svo_tree* t, const svo_volume_box* box);
-/* node records and material entries superseded by edits (svo_tree_update, svo_tree_patch_volume_gpu) since the last
-   full build: still in the arrays, no longer reachable (either may be NULL) */
+/* Patch a resident tree from a sparse list of voxel edits in HBM, on the device: n entries (x, y, z, id) in
+   svo_tree_get_blocks_gpu's layout — xyz and ids are DEVICE pointers on the tree's device, three int32 and one uint16 per
+   entry — applied in list order.  When a voxel is listed more than once its last entry decides.  A last entry of id 0
+   erases the voxel (here an id-0 entry is an edit; in svo_build_points_gpu it simply drops out); a last entry whose id the
+   tree's view does not hold is stored empty (svo_tree_patch_volume_gpu's rule).  Ids are the tree's own palette: there is
+   no palette growth.  After the call every listed voxel holds its resolved entry and every other voxel is as before.
+   Any uploaded tree (world-, terrain-, volume- or points-built, patched or not), either view, any size (every node and
+   material index is widened to 64 bits before it addresses memory).  The entries are keyed and sorted as in
+   svo_build_points_gpu; the descent starts at the deepest interior node whose region holds every edit (the anchor, the
+   only record rewritten in place) and re-emits every region an edit lies in one level down, in new child blocks
+   appended to the arrays: untouched children are copied (below a K_SOLID region: synthesised K_SOLID records), touched
+   bricks are classified from their 64 composite voxels.  As after svo_tree_patch_volume_gpu the result is the tree's
+   content, not its canonical layout: touched interior regions are not re-collapsed (records with mask 0 may result), and
+   a full one-material brick may stay a brick (svo_tree_compact_gpu restores the layout).  A touched brick that ends up
+   storing nothing clears its slot bit in its parent: no K_BRICK record with mask 0 exists.
+   The device arrays are reallocated (with the slack of a fresh upload) only when the appended tail would not fit; the
+   host image, the column ceilings (exact, over the 16 x 16-column blocks the edits touch), the tree's top row and
+   svo_tree_garbage's counts are brought up to date.  A world-built tree patched this way no longer follows its
+   svo_world: svo_tree_update on it returns SVO_ESTATE.
+   Scratch follows the edits, never the extent or the tree: 24 B per entry for the sort (as in svo_build_points_gpu) and
+   12 B for its compaction, 26 B per distinct voxel for the edit list and its column blocks, 44 B per touched region and
+   level (at most one region per edit per level), and 16 B per appended record.
+   SVO_EINVAL: NULL tree, NULL xyz or ids with n > 0, n < 0; SVO_ERANGE, before the first HIP call: n > 2^31 - 1, a tree
+   of one level; SVO_ESTATE: the tree is not uploaded, or has host edits not yet synced (svo_tree_sync); SVO_ERANGE, found
+   on the device by the key pass: an id >= the tree's palette size or a coordinate outside [0, 4^levels) (no wrap, as in
+   the builder; the message says which of the two it was); SVO_ERANGE: arrays that would pass 2^32 elements; SVO_ENOMEM:
+   no scratch.  Everything goes to scratch first: after any error the tree and its garbage counts are unchanged on host
+   and device.  n == 0 returns SVO_OK after the argument and state checks, without device work.
+   The device is synchronised on entry (the list may come from any stream, and records and ceilings are rewritten in
+   place: call it between frames); it runs on the null stream and the call is complete on return. */
+int svo_tree_patch_points_gpu(svo_tree* t, const int32_t* xyz, const uint16_t* ids, int64_t n);
+/* node records and material entries superseded by edits (svo_tree_update, svo_tree_patch_volume_gpu,
+   svo_tree_patch_points_gpu) since the last full build: still in the arrays, no longer reachable (either may be NULL) */
 int svo_tree_garbage(const svo_tree* t, uint64_t* nodes, uint64_t* mats);
-/* diagnostics (tools/volume_patch_timing.py): host-clock milliseconds of the tree's last svo_tree_patch_volume_gpu, after
-   its entry synchronisation: ms[0] the device passes (pyramid, count and write passes into scratch), ms[1] the commit to
-   the arrays and the copy back to the host image, ms[2] the host's ceiling update (with the tree's top row) */
+/* diagnostics (tools/volume_patch_timing.py, tools/points_patch_timing.py): host-clock milliseconds of the tree's last
+   svo_tree_patch_volume_gpu or svo_tree_patch_points_gpu, whichever ran last, after its entry synchronisation: ms[0] the
+   device passes (volume: pyramid, count and write passes into scratch; points: keys, sort, edit list, column blocks, count
+   and write passes), ms[1] the commit to the arrays and the copy back to the host image, ms[2] the host's ceiling update
+   (with the tree's top row) */
 int svo_tree_patch_times(const svo_tree* t, double ms[3]);
 /* Re-emit an uploaded tree, on its device, as the canonical linearisation of its own content: after the call the node
    array, the material runs, nodes_per_level, n_bricks and n_mat_bytes equal, byte for byte, what svo_build_volume_gpu

@@ -170,7 +170,7 @@ ABI_SYMBOLS = (
     "svo_tree_guard_trips", "svo_ceiling_layout", "svo_tree_device_ceilings", "svo_tree_device_ceiling_quads", "svo_tree_schedule", "svo_cast_ray_from_cam_async",
     "svo_build_id", "svo_build_volume_gpu", "svo_tree_read_volume", "svo_volume_classify_pass",
     "svo_tree_patch_volume_gpu", "svo_tree_garbage", "svo_tree_patch_times", "svo_tree_compact_gpu", "svo_tree_compact_times",
-    "svo_build_points_gpu", "svo_tree_get_blocks_gpu",
+    "svo_build_points_gpu", "svo_tree_get_blocks_gpu", "svo_tree_patch_points_gpu",
 )
 
 
@@ -257,7 +257,8 @@ def lib():
                      ("svo_tree_patch_times", [vp, C.POINTER(C.c_double)]),
                      ("svo_tree_compact_gpu", [vp]), ("svo_tree_compact_times", [vp, C.POINTER(C.c_double)]),
                      ("svo_build_points_gpu", [C.POINTER(PointsDesc), C.POINTER(vp)]),
-                     ("svo_tree_get_blocks_gpu", [vp, vp, C.c_int64, vp, vp])):
+                     ("svo_tree_get_blocks_gpu", [vp, vp, C.c_int64, vp, vp]),
+                     ("svo_tree_patch_points_gpu", [vp, vp, vp, C.c_int64])):
         if hasattr(L, name):
             getattr(L, name).argtypes = at
     L.svo_build_terrain.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
@@ -560,7 +561,7 @@ class Tree:
         0 = empty), or a numpy uint16 array of that shape (uploaded through torch); palette: [(flags, color, metadata)]
         as Tree.palette() returns it, entry 0 the empty block; origin: the world position of voxels[0, 0, 0] as
         (x, y, z).  Voxels outside the box are empty.  Such a tree has no World behind it (update() needs one): it is
-        changed in HBM by patch_volume()."""
+        changed in HBM by patch_volume() or patch_points()."""
         d, keep = cls.volume_desc(levels, voxels, palette, origin, view, device)
         h = C.c_void_p()
         _check(lib().svo_build_volume_gpu(C.byref(d), C.byref(h)), "svo_build_volume_gpu")
@@ -615,7 +616,7 @@ class Tree:
         tensor (n, 3) of positions within the extent, or a numpy int32 array of that shape (uploaded through torch); ids:
         n palette ids, torch.uint16 / torch.int16 (the bits are the ids) or numpy; palette: [(flags, color, metadata)],
         entry 0 the empty block.  The points are applied in order: a voxel's last entry decides, id 0 erases.  Such a
-        tree has no World behind it (update() fails): it is changed in HBM by patch_volume()."""
+        tree has no World behind it (update() fails): it is changed in HBM by patch_points() or patch_volume()."""
         xyz, ids = cls._device_points(xyz, ids, device)
         pal = (Block * max(1, len(palette)))()
         for i, (f, c, m) in enumerate(palette):
@@ -676,15 +677,37 @@ class Tree:
         _check(lib().svo_tree_patch_volume_gpu(self._h, C.byref(b)), "svo_tree_patch_volume_gpu")
         return self
 
+    def patch_points(self, xyz, ids):
+        """svo_tree_patch_points_gpu: apply a list of voxel edits to this (uploaded) tree, on the device.  xyz: a
+        contiguous CUDA int32 tensor (n, 3) of positions within the extent on the tree's device, or a numpy int32 array
+        of that shape (uploaded through torch); ids: n ids of the tree's own palette, torch.uint16 / torch.int16 (the
+        bits are the ids) or numpy.  The entries are applied in order: a voxel's last entry decides, id 0 erases, an id
+        the tree's view does not store becomes empty.  Every other voxel stays as it is; the host image, the ceilings
+        and garbage() are brought up to date, and the call is complete on return.  The cost follows the number of
+        edits, not the extent.  Any uploaded tree may be patched; a World-built one no longer follows its World
+        afterwards (update() then fails)."""
+        dev = self.info().device
+        if dev < 0:
+            raise SvoError("svo_tree_patch_points_gpu failed (-4): tree not uploaded (svo_upload)")
+        xyz, ids = self._device_points(xyz, ids, dev)
+        if ids is None:
+            raise ValueError("ids: a torch tensor or a numpy uint16 array")
+        n = int(xyz.shape[0])
+        _check(lib().svo_tree_patch_points_gpu(self._h, C.c_void_p(xyz.data_ptr()) if n else None,
+                                               C.c_void_p(ids.data_ptr()) if n else None, n), "svo_tree_patch_points_gpu")
+        del xyz, ids
+        return self
+
     def garbage(self):
-        """svo_tree_garbage: (node records, material entries) superseded by update() / patch_volume() since the last
+        """svo_tree_garbage: (node records, material entries) superseded by update() / patch_volume() / patch_points() since the last
         full build or compact(): when they outweigh the tree, compact() pays"""
         n, m = C.c_uint64(), C.c_uint64()
         _check(lib().svo_tree_garbage(self._h, C.byref(n), C.byref(m)), "svo_tree_garbage")
         return n.value, m.value
 
     def patch_times(self):
-        """svo_tree_patch_times: host-clock ms of the last patch_volume() — (device passes, commit + host image, ceilings)"""
+        """svo_tree_patch_times: host-clock ms of the last patch_volume() or patch_points() — (device passes, commit + host
+        image, ceilings)"""
         ms = (C.c_double * 3)()
         _check(lib().svo_tree_patch_times(self._h, ms), "svo_tree_patch_times")
         return tuple(ms)

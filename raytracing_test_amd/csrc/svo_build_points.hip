@@ -5,8 +5,9 @@
 //   * key pass: one lane per point computes its 64-bit cell key (svo_points_source.h) and checks the id and the
 //     coordinates (an atomicOr flag, read on the host before anything else is allocated);
 //   * a stable radix sort of (key, id) over the key's 6 * levels bits (hipCUB): the entries of a voxel end up next to
-//     each other in list order, so the last of each run of equal keys is the voxel's content; it is stored unless its
-//     id is 0 or out of the tree's view, and the stored voxels are compacted to level 0;
+//     each other in list order (both in svo_point_keys.h, shared with svo_patch_points.hip), so the last of each run
+//     of equal keys is the voxel's content; it is stored unless its id is 0 or out of the tree's view, and the stored
+//     voxels are compacted to level 0;
 //   * class levels, bottom up: level k's cells are the runs of level k - 1 under key >> 6; a run of 64 children that
 //     all carry one id has that id for its class, every other run is MIXED (absent cells are empty: no class);
 //   * emission, top down: svo_build_emit.h over PointSource, which finds a cell by binary search in its level.
@@ -24,28 +25,13 @@
 #include "svo_build_emit.h"
 #include "svo_hip.h"
 #include "svo_internal.h"
+#include "svo_point_keys.h"
 #include "svo_points_source.h"
 #include "svo_tree_descent.h"
 
 using namespace svo;
 
 namespace {
-
-constexpr int32_t kBadId = 1, kBadCoord = 2;  // bits of the key pass's flag word
-
-// keys and ids of points 0..n; a bad point gets key 0 (nothing is built from the keys then)
-__global__ void k_point_keys(const int32_t* xyz, const uint16_t* ids, int64_t n, int32_t levels, uint32_t n_pal, uint64_t* keys,
-                             uint16_t* vals, int32_t* bad) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t E = 1u << (2 * levels);
-    const uint32_t x = (uint32_t)xyz[3 * i], y = (uint32_t)xyz[3 * i + 1], z = (uint32_t)xyz[3 * i + 2];  // (negative: above E)
-    const uint32_t id = ids[i];
-    const int32_t b = (id >= n_pal ? kBadId : 0) | ((x >= E || y >= E || z >= E) ? kBadCoord : 0);
-    if (b) atomicOr(bad, b);
-    keys[i] = b ? 0ull : voxel_key(x, y, z, levels);
-    vals[i] = (uint16_t)id;
-}
 
 // sorted entries: 1 for the last entry of a voxel when it is stored
 __global__ void k_point_winners(const uint64_t* keys, const uint16_t* vals, int64_t n, const uint32_t* in_view, uint32_t* keep) {
@@ -108,8 +94,6 @@ __global__ void k_get_blocks(DevTree P, const int32_t* xyz, int64_t i0, int64_t 
     ids[i] = (uint16_t)old_voxel(P, (uint32_t)xyz[3 * i] & mk, (uint32_t)xyz[3 * i + 1] & mk, (uint32_t)xyz[3 * i + 2] & mk);
 }
 
-inline dim3 lanes(int64_t n) { return dim3(blocks_for(n, 256)); }  // n < 2^31 lanes: fewer than 2^32 work-items
-
 // argument checks of a points desc: before any HIP call, so that a machine without a GPU still reports them
 int check_points(const svo_points_desc* p, const std::string& w) {
     if (!p) SVO_FAIL(SVO_EINVAL, w + ": desc is NULL");
@@ -129,36 +113,12 @@ int build_levels(const svo_points_desc* p, const uint32_t* in_view, Pool& pool, 
     *bad = 0;
     const int64_t n = p->n;
     if (n == 0) return SVO_OK;
-    int32_t* dbad;
-    uint64_t* k0;
-    uint16_t* v0;
-    int rc = pool.alloc(&dbad, 1);
-    if (!rc) rc = pool.alloc(&k0, (size_t)n);
-    if (!rc) rc = pool.alloc(&v0, (size_t)n);
-    if (rc) return rc;
-    HIP_TRY(hipMemset(dbad, 0, 4), SVO_EDEVICE);
-    hipLaunchKernelGGL(k_point_keys, lanes(n), dim3(256), 0, nullptr, p->xyz, p->ids, n, p->levels, p->n_palette, k0, v0, dbad);
-    HIP_TRY(hipGetLastError(), SVO_EDEVICE);
-    HIP_TRY(hipMemcpy(bad, dbad, 4, hipMemcpyDeviceToHost), SVO_EDEVICE);
-    if (*bad) return SVO_OK;
-
-    // the stable sort, between two pairs of buffers
-    uint64_t* k1;
-    uint16_t* v1;
-    rc = pool.alloc(&k1, (size_t)n);
-    if (!rc) rc = pool.alloc(&v1, (size_t)n);
-    if (rc) return rc;
-    hipcub::DoubleBuffer<uint64_t> dk(k0, k1);
-    hipcub::DoubleBuffer<uint16_t> dv(v0, v1);
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dk, dv, n, 0, 6 * p->levels), SVO_EDEVICE);
-    char* tmp;
-    rc = pool.alloc(&tmp, tb);
-    if (rc) return rc;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tb, dk, dv, n, 0, 6 * p->levels), SVO_EDEVICE);
-    const uint64_t* keys = dk.Current();
-    const uint16_t* vals = dv.Current();
-    uint64_t* off = dk.Alternate();  // the sort's other key buffer: the scans' output from here on (n entries at most)
+    SortedPoints P;
+    int rc = sort_point_keys(p->xyz, p->ids, n, p->levels, p->n_palette, pool, &P, bad);
+    if (rc || *bad) return rc;
+    const uint64_t* keys = P.keys;
+    const uint16_t* vals = P.vals;
+    uint64_t* off = P.spare;  // the sort's other key buffer: the scans' output from here on (n entries at most)
     uint32_t* flag;
     rc = pool.alloc(&flag, (size_t)n);
     if (rc) return rc;

@@ -94,24 +94,24 @@ int svo::sync_ceilings(svo_tree* t) {
     const int32_t n = t->ceil_levels;
     std::vector<std::array<int64_t, 4>> rects;
     rects.swap(t->ceil_dirty);
-    for (const auto& r : rects) {
-        int64_t zr[kCeilMax][2], qr[2];
-        try {
-            ceil_tables_update(t, n, r, zr, qr);
-        } catch (const std::bad_alloc&) {
-            SVO_FAIL(SVO_ENOMEM, "column ceilings: out of host memory");
+    CeilRows rows;
+    try {
+        ceil_tables_update_all(t, n, rects, &rows);
+    } catch (const std::bad_alloc&) {
+        SVO_FAIL(SVO_ENOMEM, "column ceilings: out of host memory");
+    }
+    {
+        const int64_t w = (int64_t)1 << (2 * (t->levels - kCeilK0));
+        for (const auto& q : rows.quads) {
+            const int64_t lo = q.first * w, cnt = (q.second - q.first) * w;
+            HIP_TRY(hipMemcpy(reinterpret_cast<uint64_t*>(t->d_ceilq) + lo, t->ceilq_host.data() + lo, cnt * sizeof(uint64_t),
+                              hipMemcpyHostToDevice), SVO_EDEVICE);
         }
-        {
-            const int64_t rows = (int64_t)1 << (2 * (t->levels - kCeilK0));
-            const int64_t lo = qr[0] * rows, cnt = (qr[1] - qr[0]) * rows;
-            if (cnt > 0)
-                HIP_TRY(hipMemcpy(reinterpret_cast<uint64_t*>(t->d_ceilq) + lo, t->ceilq_host.data() + lo, cnt * sizeof(uint64_t),
-                                  hipMemcpyHostToDevice), SVO_EDEVICE);
-        }
-        for (int32_t j = 0; j < n; j++) {
-            const int64_t rows = (int64_t)1 << (2 * (t->levels - kCeilK0 - j));
-            const int64_t lo = t->ceil_off[j] + zr[j][0] * rows, cnt = (zr[j][1] - zr[j][0]) * rows;
-            if (cnt <= 0) continue;
+    }
+    for (int32_t j = 0; j < n; j++) {
+        const int64_t w = (int64_t)1 << (2 * (t->levels - kCeilK0 - j));
+        for (const auto& z : rows.level[j]) {
+            const int64_t lo = t->ceil_off[j] + z.first * w, cnt = (z.second - z.first) * w;
             HIP_TRY(hipMemcpy(reinterpret_cast<int16_t*>(t->d_ceil) + lo, t->ceil_host.data() + lo, cnt * sizeof(int16_t),
                               hipMemcpyHostToDevice), SVO_EDEVICE);
             HIP_TRY(hipMemcpy(reinterpret_cast<uint32_t*>(t->d_ceilp) + lo, t->ceilp_host.data() + lo, cnt * sizeof(uint32_t),

@@ -82,8 +82,8 @@ struct svo_tree {
     uint64_t synced_nodes = 0, synced_mats = 0;  // prefix of nodes / mats already in HBM
     std::vector<uint32_t> dirty_nodes;           // rewritten in place below synced_nodes
     bool palette_dirty = false, full_upload = false;
-    // svo_tree_patch_volume_gpu has changed the tree: it no longer mirrors the svo_world it was built from, and
-    // svo_tree_update refuses it
+    // svo_tree_patch_volume_gpu or svo_tree_patch_points_gpu has changed the tree: it no longer mirrors the svo_world it
+    // was built from, and svo_tree_update refuses it
     bool volume_patched = false;
     // built by svo_build_points_gpu: no svo_world holds its content, and svo_tree_update refuses it
     bool no_world = false;
@@ -163,6 +163,6 @@ void tree_release_device(svo_tree* t);  // svo_device.hip
 // already equal to their first nodes.size() / mats.size() elements): svo_device.hip
 int adopt_device(svo_tree* t, int32_t device, void* d_nodes, uint64_t node_cap, void* d_mats, uint64_t mat_cap);
 // the ceiling tables over the rectangles of svo_tree.ceil_dirty recomputed from the host image, the changed rows sent to the
-// device buffers already there (svo_tree_sync's last step, and svo_tree_patch_volume_gpu's): svo_device.hip
+// device buffers already there (svo_tree_sync's last step, and the device-side patches'): svo_device.hip
 int sync_ceilings(svo_tree* t);
 }

@@ -145,7 +145,7 @@ extern "C" int svo_tree_update(svo_tree* t, const svo_world* w, const int32_t* x
     if (t->levels != w->levels) SVO_FAIL(SVO_EINVAL, "svo_tree_update: tree and world differ in levels");
     if (level < 1 || level > w->levels + 1) SVO_FAIL(SVO_EINVAL, "svo_tree_update: level out of range");
     if (t->volume_patched)
-        SVO_FAIL(SVO_ESTATE, "svo_tree_update: the tree was patched by svo_tree_patch_volume_gpu and no longer follows a world");
+        SVO_FAIL(SVO_ESTATE, "svo_tree_update: the tree was patched by svo_tree_patch_volume_gpu or svo_tree_patch_points_gpu and no longer follows a world");
     if (t->no_world) SVO_FAIL(SVO_ESTATE, "svo_tree_update: the tree was built by svo_build_points_gpu and follows no world");
     const int L = t->levels;
     const int de = level - 1;  // depth of the edited region (putBlock's `level--`)

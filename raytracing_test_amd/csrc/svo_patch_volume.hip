@@ -14,7 +14,8 @@
 // one list of work items per level holds the cut regions (with what they held before) and the plain MIXED ones.  The
 // descent starts at the anchor the host finds on its image (svo_plan.cpp patch_anchor), whose record is the only one
 // rewritten in place.  Everything is written to scratch first: the totals are known, and every id checked, before the
-// tree is touched, and the arrays are reallocated (emit_tree's slack rule) only when the tail would not fit.
+// tree is touched, and the arrays are reallocated (emit_tree's slack rule) only when the tail would not fit
+// (svo_patch_commit.h, shared with svo_patch_points.hip).
 // Every node and material index is widened to 64 bits before it addresses memory: trees above 2^28 nodes take the same
 // kernels.
 #include <hip/hip_runtime.h>
@@ -29,6 +30,7 @@
 #include "svo_build_emit.h"
 #include "svo_hip.h"
 #include "svo_internal.h"
+#include "svo_patch_commit.h"
 #include "svo_plan.h"
 #include "svo_tree_descent.h"
 #include "svo_volume_pyramid.h"
@@ -179,38 +181,6 @@ __global__ void k_patch_brick_write(DevPatch P, const Item* cur, int64_t r0, int
     const uint32_t first = (uint32_t)__shfl((int)c, (int)__builtin_ctzll(solid | (1ull << 63)));
     if (!uni && c != G_EMPTY) mats[moff[r] + (uint64_t)__popcll(solid & ((1ull << v) - 1ull))] = (uint16_t)c;
     if (v == 0) out[R.node] = uni ? Node{solid, 0u, K_BRICK | K_UNIFORM | (first << 16)} : Node{solid, (uint32_t)(mbase + moff[r]), K_BRICK};
-}
-
-// the device arrays grown to hold `need_n` nodes and `need_m` material entries (emit_tree's slack rule), the first `keep_n` /
-// `keep_m` elements kept
-int grow_device(svo_tree* t, uint64_t need_n, uint64_t keep_n, uint64_t need_m, uint64_t keep_m) {
-    if (need_n > t->dev_node_cap) {
-        const uint64_t cap = std::min<uint64_t>(need_n + need_n / 8 + 65536, 1ull << 32);
-        void* p = nullptr;
-        HIP_TRY(hipMalloc(&p, cap * sizeof(Node)), SVO_ENOMEM);
-        if (hipMemcpy(p, t->d_nodes, keep_n * sizeof(Node), hipMemcpyDeviceToDevice) != hipSuccess) {
-            (void)hipFree(p);
-            SVO_FAIL(SVO_EDEVICE, "svo_tree_patch_volume_gpu: device copy failed");
-        }
-        (void)hipFree(t->d_nodes);
-        t->d_nodes = p;
-        t->device_bytes += (cap - t->dev_node_cap) * sizeof(Node);
-        t->dev_node_cap = cap;
-    }
-    if (need_m > t->dev_mat_cap) {
-        const uint64_t cap = std::min<uint64_t>(need_m + need_m / 8 + 65536, 1ull << 32);
-        void* p = nullptr;
-        HIP_TRY(hipMalloc(&p, cap * sizeof(uint16_t)), SVO_ENOMEM);
-        if (keep_m && hipMemcpy(p, t->d_mats, keep_m * sizeof(uint16_t), hipMemcpyDeviceToDevice) != hipSuccess) {
-            (void)hipFree(p);
-            SVO_FAIL(SVO_EDEVICE, "svo_tree_patch_volume_gpu: device copy failed");
-        }
-        (void)hipFree(t->d_mats);
-        t->d_mats = p;
-        t->device_bytes += (cap - t->dev_mat_cap) * sizeof(uint16_t);
-        t->dev_mat_cap = cap;
-    }
-    return SVO_OK;
 }
 
 }  // namespace
@@ -389,35 +359,14 @@ extern "C" int svo_tree_patch_volume_gpu(svo_tree* t, const svo_volume_box* box)
     const auto clock1 = std::chrono::steady_clock::now();
 
     // the totals are known and nothing of the tree has changed yet: room, then the tail, then the anchor's record
-    const uint64_t add = used - 1, total_n = nbase + add, total_m = mbase + n_mats;
-    try {  // (the host vectors grow with the device arrays' slack: an exact reserve would copy the whole image at every patch)
-        if (total_n > t->nodes.capacity()) t->nodes.reserve(total_n + total_n / 8 + 65536);
-        if (total_m > t->mats.capacity()) t->mats.reserve(total_m + total_m / 8 + 65536);
-    } catch (const std::bad_alloc&) {
-        SVO_FAIL(SVO_ENOMEM, "svo_tree_patch_volume_gpu: out of host memory");
-    }
-    rc = grow_device(t, total_n, anchor.whole ? 0 : nbase, total_m, mbase);
+    rc = commit_patch(t, who, PatchTail{out, used - 1, mats, n_mats, anchor.node, nbase, mbase, anchor.whole});
     if (rc) return rc;
-    Node* dn = reinterpret_cast<Node*>(t->d_nodes);
-    uint16_t* dm = reinterpret_cast<uint16_t*>(t->d_mats);
-    if (add) HIP_TRY(hipMemcpy(dn + nbase, out + 1, add * sizeof(Node), hipMemcpyDeviceToDevice), SVO_EDEVICE);
-    if (n_mats) HIP_TRY(hipMemcpy(dm + mbase, mats, n_mats * sizeof(uint16_t), hipMemcpyDeviceToDevice), SVO_EDEVICE);
-    HIP_TRY(hipMemcpy(dn + anchor.node, out, sizeof(Node), hipMemcpyDeviceToDevice), SVO_EDEVICE);
-    // the host image stays the mirror of HBM
-    t->nodes.resize(total_n);
-    t->mats.resize(total_m);
-    if (add) HIP_TRY(hipMemcpy(t->nodes.data() + nbase, dn + nbase, add * sizeof(Node), hipMemcpyDeviceToHost), SVO_EDEVICE);
-    if (n_mats) HIP_TRY(hipMemcpy(t->mats.data() + mbase, dm + mbase, n_mats * sizeof(uint16_t), hipMemcpyDeviceToHost), SVO_EDEVICE);
-    HIP_TRY(hipMemcpy(t->nodes.data() + anchor.node, dn + anchor.node, sizeof(Node), hipMemcpyDeviceToHost), SVO_EDEVICE);
-    t->synced_nodes = total_n;
-    t->synced_mats = total_m;
     if (anchor.whole) {
         t->garbage_nodes = t->garbage_mats = 0;
     } else {
         t->garbage_nodes += gnodes;
         t->garbage_mats += gmats;
     }
-    t->volume_patched = true;
     const auto clock2 = std::chrono::steady_clock::now();
     {
         std::lock_guard<std::mutex> lock(t->top_mu);

@@ -216,10 +216,46 @@ int32_t ceil_tables_build(svo_tree* t) {
     return n;
 }
 
+// row intervals [first, last) sorted and joined where they overlap or touch
+static void merge_rows(std::vector<std::pair<int64_t, int64_t>>& v) {
+    std::sort(v.begin(), v.end());
+    size_t k = 0;
+    for (size_t i = 0; i < v.size(); i++) {
+        if (v[i].second <= v[i].first) continue;
+        if (k > 0 && v[i].first <= v[k - 1].second) v[k - 1].second = std::max(v[k - 1].second, v[i].second);
+        else v[k++] = v[i];
+    }
+    v.resize(k);
+}
+
 void ceil_tables_update(svo_tree* t, int32_t n, const std::array<int64_t, 4>& r, int64_t zr[kCeilMax][2], int64_t qr[2]) {
     ceilings_update_rect(t, t->ceil_host, t->ceil_off, n, r[0], r[1], r[2], r[3]);
     ceil_pairs(t, n, r[0], r[1], r[2], r[3], zr);
     ceil_quads(t, n, r[0], r[1], r[2], r[3], qr);
+}
+
+void ceil_tables_update_all(svo_tree* t, int32_t n, const std::vector<std::array<int64_t, 4>>& rects, CeilRows* rows) {
+    // the quads of a rectangle are those of the coarsest level's blocks holding it: each distinct span of such blocks is
+    // recomputed once, after every rectangle's ceilings are final (a list of scattered edits has thousands of rectangles
+    // in a few hundred spans)
+    const int32_t csh = 2 * (kCeilK0 + n - 1);
+    std::vector<std::array<int64_t, 4>> spans;
+    for (const auto& r : rects) {
+        int64_t zr[kCeilMax][2];
+        ceilings_update_rect(t, t->ceil_host, t->ceil_off, n, r[0], r[1], r[2], r[3]);
+        ceil_pairs(t, n, r[0], r[1], r[2], r[3], zr);
+        for (int32_t j = 0; j < n; j++) rows->level[j].push_back({zr[j][0], zr[j][1]});
+        spans.push_back({r[0] >> csh, r[1] >> csh, (r[2] - 1) >> csh, (r[3] - 1) >> csh});
+    }
+    std::sort(spans.begin(), spans.end());
+    spans.erase(std::unique(spans.begin(), spans.end()), spans.end());
+    for (const auto& s : spans) {
+        int64_t qr[2];
+        ceil_quads(t, n, s[0] << csh, s[1] << csh, (s[2] + 1) << csh, (s[3] + 1) << csh, qr);
+        rows->quads.push_back({qr[0], qr[1]});
+    }
+    for (int32_t j = 0; j < n; j++) merge_rows(rows->level[j]);
+    merge_rows(rows->quads);
 }
 
 std::vector<std::pair<uint32_t, uint32_t>> dirty_runs(std::vector<uint32_t>& dirty) {
@@ -269,6 +305,67 @@ PatchAnchor patch_anchor(const Node* nodes, int32_t levels, const int32_t lo[3],
     }
     a.old = a.node;
     return a;
+}
+
+PatchAnchor points_anchor(const Node* nodes, int32_t levels, uint64_t key_first, uint64_t key_last) {
+    PatchAnchor a{0u, 0, {0, 0, 0}, P_NODE, 0u, false};
+    if (node_kind(nodes[0].info) != K_INTERIOR) {  // a lone SOLID root, as in patch_anchor
+        a.kind = P_UNIFORM;
+        a.old = node_material(nodes[0].info);
+        return a;
+    }
+    while (a.depth < levels - 2) {  // (a child at depth levels - 1 is a BRICK or SOLID record)
+        const int sh = 6 * (levels - 1 - a.depth);
+        const uint32_t sl = (uint32_t)((key_first >> sh) & 63ull);
+        if ((key_first >> sh) != (key_last >> sh)) break;  // the edits part here
+        const Node& n = nodes[a.node];
+        if (!((n.mask >> sl) & 1ull)) break;
+        const uint32_t ci = packed_index(n, sl);
+        if (node_kind(nodes[ci].info) != K_INTERIOR) break;
+        const int32_t cs = 1 << (2 * (levels - 1 - a.depth));
+        a.node = ci;
+        a.depth++;
+        a.o[0] += (int32_t)(sl & 3u) * cs;
+        a.o[1] += (int32_t)((sl >> 2) & 3u) * cs;
+        a.o[2] += (int32_t)(sl >> 4) * cs;
+    }
+    a.old = a.node;
+    return a;
+}
+
+std::vector<std::array<int64_t, 4>> ceil_block_rects(std::vector<uint64_t>& blocks) {
+    std::vector<std::array<int64_t, 4>> rects;
+    std::sort(blocks.begin(), blocks.end());
+    const int64_t w = (int64_t)1 << (2 * kCeilK0);
+    std::vector<size_t> prev, cur;  // the rectangles (indices) that end at the row before / at the current row, ascending in x
+    size_t pi = 0;
+    int64_t row = -2;
+    for (size_t i = 0; i < blocks.size();) {
+        const int64_t bz = (int64_t)(blocks[i] >> 32), bx0 = (int64_t)(blocks[i] & 0xFFFFFFFFull);
+        int64_t bx1 = bx0 + 1;
+        size_t j = i + 1;
+        while (j < blocks.size() && (int64_t)(blocks[j] >> 32) == bz && (int64_t)(blocks[j] & 0xFFFFFFFFull) <= bx1) {
+            bx1 = std::max(bx1, (int64_t)(blocks[j] & 0xFFFFFFFFull) + 1);  // (a duplicate keeps bx1)
+            j++;
+        }
+        i = j;
+        if (bz != row) {  // a new row: only the rectangles of the row just before it can grow into it
+            if (bz == row + 1) prev.swap(cur);
+            else prev.clear();
+            cur.clear();
+            pi = 0;
+            row = bz;
+        }
+        while (pi < prev.size() && rects[prev[pi]][0] < bx0 * w) pi++;
+        if (pi < prev.size() && rects[prev[pi]][0] == bx0 * w && rects[prev[pi]][2] == bx1 * w) {  // the same span one row up
+            rects[prev[pi]][3] = (bz + 1) * w;
+            cur.push_back(prev[pi++]);
+        } else {
+            cur.push_back(rects.size());
+            rects.push_back({bx0 * w, bz * w, bx1 * w, (bz + 1) * w});
+        }
+    }
+    return rects;
 }
 
 namespace {

@@ -39,6 +39,15 @@ CastInstance cast_instance(const CastRequest& q);
 // std::bad_alloc.
 int32_t ceil_tables_build(svo_tree* t);
 void ceil_tables_update(svo_tree* t, int32_t n, const std::array<int64_t, 4>& r, int64_t zr[kCeilMax][2], int64_t qr[2]);
+// The same over every rectangle of svo_tree.ceil_dirty at once (sync_ceilings), with the same tables as one call of
+// ceil_tables_update per rectangle, in order, leaves.  The rows rewritten come back as sorted, disjoint intervals
+// [first, last): one rectangle gives the one interval per table ceil_tables_update reports.  The rectangles of a list of
+// scattered edits (svo_tree_patch_points_gpu) share their coarsest blocks: the quads of each distinct span of those are
+// recomputed once, after every rectangle's ceilings are final, and rows that several rectangles rewrite are sent once.
+struct CeilRows {
+    std::vector<std::pair<int64_t, int64_t>> level[kCeilMax], quads;
+};
+void ceil_tables_update_all(svo_tree* t, int32_t n, const std::vector<std::array<int64_t, 4>>& rects, CeilRows* rows);
 
 // the tree's rewritten records (svo_tree.dirty_nodes, sorted here) as runs [first, last] of consecutive indices
 std::vector<std::pair<uint32_t, uint32_t>> dirty_runs(std::vector<uint32_t>& dirty);
@@ -70,6 +79,17 @@ PatchAnchor patch_anchor(const Node* nodes, int32_t levels, const int32_t lo[3],
 // box cuts (it is rewritten at the tail), every subtree wholly inside the box, the material run of every brick the box meets
 void patch_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const int32_t lo[3], const int32_t hi[3], uint64_t* n_nodes,
                       uint64_t* n_mats);
+
+// svo_tree_patch_points_gpu (svo_patch_points.hip) applies a sorted list of edits, each a voxel's cell key (6 bits per
+// level, the slot bits z<<4 | y<<2 | x with the top level first).  Its anchor is the deepest K_INTERIOR record, at depth
+// <= levels - 2, whose region holds every edit: down from the root along the 6-bit digits the list's first and last key
+// have in common, stopping as patch_anchor does at an absent slot, at a K_SOLID or K_BRICK child, and at a lone K_SOLID
+// root (kind P_UNIFORM).  It is never whole: a list does not restart the arrays.
+PatchAnchor points_anchor(const Node* nodes, int32_t levels, uint64_t key_first, uint64_t key_last);
+// The 16 x 16-column blocks a list of edits touches, each as (bz << 32) | bx in block units (any order, duplicates allowed),
+// merged into column rectangles {x0, z0, x1, z1} in voxels for svo_tree.ceil_dirty: runs of adjacent blocks within a block
+// row, and runs of equal span in consecutive rows joined into one rectangle.  `blocks` is sorted in place.
+std::vector<std::array<int64_t, 4>> ceil_block_rects(std::vector<uint64_t>& blocks);
 
 // A schedule predicts a frame from the last one: a camera that turned more than kSchedTurn or moved more than kSchedMove
 // voxels since runs the default order (and re-primes).  Measured (tools/shade_motion.py, r04_ax): a still view 0.462 ->

@@ -118,7 +118,10 @@ __device__ __forceinline__ uint32_t lookup(const CastParams& P, const Mem& mem, 
             par.mask = path.mask(da);
             par.ref = path.ref(da);
             par.sh = (uint32_t)(2 * (P.levels - 1 - da));
-            if (STATS) st.path_starts++;
+            if (STATS) {
+                st.path_starts++;
+                if (da == 0) st.root_starts++;  // (back to the root, which stands in the path at depth 0: svo_trace.h)
+            }
         }
         sh_out = par.sh;
         const uint64_t t = slot_top(par.mask, child_slot(w[0], w[1], w[2], par.sh));

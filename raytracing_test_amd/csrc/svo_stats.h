@@ -11,8 +11,8 @@ struct Stats {
     uint32_t bricks;         // brick visits
     uint32_t wv_iters, wv_brick;  // wave-level executions (counted on the first active lane): outer
                                   // loop iterations, brick voxel steps
-    uint32_t root_starts, cache_empty;  // lookups started at the root; lookups answered by the
-                                        // parent mask
+    uint32_t root_starts, cache_empty;  // lookups started at the root (a load of it, or a path restart at depth 0, where
+                                        // it stands once a trace has seeded it); lookups answered by the parent mask
     uint32_t path_starts;                          // lookups restarted from the LDS path
     uint32_t wv_skips, wv_descents;                // wave-level crossings, descent levels
     uint32_t no_progress;                          // loop iterations that consumed no budget (the guard's trips: 0)

@@ -32,7 +32,7 @@ extern "C" {
                              svo_volume_classify_pass, svo_tree_patch_volume_gpu, svo_tree_garbage,
                              svo_tree_patch_times, svo_tree_compact_gpu, svo_tree_compact_times,
                              svo_build_points_gpu, svo_tree_get_blocks_gpu,
-                             svo_tree_patch_points_gpu */
+                             svo_tree_patch_points_gpu, svo_tree_list_voxels_gpu */
 
 enum {
     SVO_OK = 0,
@@ -221,6 +221,37 @@ int svo_build_points_gpu(const svo_points_desc* p, svo_tree** out);
    tree, however built, patched or not.  SVO_EINVAL: NULL tree, NULL buffers with n > 0, n < 0; SVO_ESTATE: the tree is
    not uploaded; n == 0 returns SVO_OK without a launch */
 int svo_tree_get_blocks_gpu(const svo_tree* t, const int32_t* xyz, int64_t n, uint16_t* ids, void* hip_stream);
+/* The voxels the tree stores (its view) inside the box origin .. origin + (nx, ny, nz), listed in HBM as (x, y, z, id): the
+   inverse of svo_build_points_gpu, read from the device copy as svo_tree_get_blocks_gpu reads it.  origin == NULL means the
+   whole extent (nx, ny, nz are then ignored); otherwise origin >= 0, origin + n <= 4^levels and positive dimensions (no
+   wrap: the patch box's rule).  xyz and ids are DEVICE buffers in svo_tree_get_blocks_gpu's layout (three int32 and one
+   uint16 per entry) with room for `cap` entries; *n is a HOST value, the exact number of stored voxels in the box, a 64-bit
+   count, set on SVO_OK and on the capacity errors below.
+   Order: the output is strictly increasing in the point builder's key — 6 bits per level, the top level first, each
+   level's slot z<<4 | y<<2 | x of that level's base-4 digits of the coordinates.  That is the order in which
+   svo_build_points_gpu holds a list after its sort, and the tree's own depth-first slot order; no sort takes place.
+   Count only: xyz == NULL && ids == NULL && cap == 0 writes nothing and returns the count.  Uniform regions are never
+   expanded for it: a K_SOLID region contributes the volume of its intersection with the box in closed form (the count of
+   a solid 16384^3 root is 2^42).
+   The cost follows the tree and the output, never the box's volume: records are reached top down only where their region
+   meets the box (one list per depth), every record's total is folded bottom up, the output offsets are handed down as
+   exclusive scans over the 64 slots, and the voxels are written by one wavefront per brick and, for K_SOLID regions, one
+   lane per voxel that unranks its index digit by digit.  No position is looked up from the root.
+   Scratch in HBM, freed on return: 60 B per reached record (a 16-B copy of the record, 16 B for its region's first voxel,
+   8 B each for its total and its output offset, and 4 + 8 B for a count and its scan, used twice), 16 B per K_SOLID
+   region written from, and hipCUB's scan temporaries.  A count-only call takes 52 B per reached record.
+   Any uploaded tree: world-, terrain-, volume- or points-built, patched or not, compacted or not, either view, 1 to 7
+   levels, in every layout the patches leave (records with mask 0, full one-material bricks that stayed bricks,
+   superseded records, which are never reached).  The tree is only read: host image, ceilings, garbage counts and
+   schedules stay as they are.
+   SVO_EINVAL: NULL t or n; one of xyz / ids NULL with the other set or with cap > 0; cap < 0; a non-positive dimension; a
+   box that leaves the extent.  SVO_ESTATE: the tree is not uploaded.  SVO_ERANGE, with *n set and nothing written: the
+   count exceeds 2^31 - 1 when buffers are given, or the count exceeds cap.  SVO_ENOMEM: no scratch.  Arguments and state
+   are checked before the first HIP call.
+   The call runs on hip_stream and waits for it before returning (the count is a host value); it does not synchronise
+   the device. */
+int svo_tree_list_voxels_gpu(const svo_tree* t, const int32_t origin[3], int32_t nx, int32_t ny, int32_t nz,
+                             int32_t* xyz, uint16_t* ids, int64_t cap, int64_t* n, void* hip_stream);
 /* Patch a resident tree from a dense box of voxels in HBM, on the device: after the call the tree's content inside the
    box is exactly `voxels` (ids the tree's view does not hold are stored empty, as in svo_build_volume_gpu); everything
    outside the box is as before.  Any uploaded tree (volume-, terrain- or world-built), either view, any size (nodes are

@@ -170,7 +170,7 @@ ABI_SYMBOLS = (
     "svo_tree_guard_trips", "svo_ceiling_layout", "svo_tree_device_ceilings", "svo_tree_device_ceiling_quads", "svo_tree_schedule", "svo_cast_ray_from_cam_async",
     "svo_build_id", "svo_build_volume_gpu", "svo_tree_read_volume", "svo_volume_classify_pass",
     "svo_tree_patch_volume_gpu", "svo_tree_garbage", "svo_tree_patch_times", "svo_tree_compact_gpu", "svo_tree_compact_times",
-    "svo_build_points_gpu", "svo_tree_get_blocks_gpu", "svo_tree_patch_points_gpu",
+    "svo_build_points_gpu", "svo_tree_get_blocks_gpu", "svo_tree_patch_points_gpu", "svo_tree_list_voxels_gpu",
 )
 
 
@@ -258,7 +258,8 @@ def lib():
                      ("svo_tree_compact_gpu", [vp]), ("svo_tree_compact_times", [vp, C.POINTER(C.c_double)]),
                      ("svo_build_points_gpu", [C.POINTER(PointsDesc), C.POINTER(vp)]),
                      ("svo_tree_get_blocks_gpu", [vp, vp, C.c_int64, vp, vp]),
-                     ("svo_tree_patch_points_gpu", [vp, vp, vp, C.c_int64])):
+                     ("svo_tree_patch_points_gpu", [vp, vp, vp, C.c_int64]),
+                     ("svo_tree_list_voxels_gpu", [vp, C.POINTER(i32), i32, i32, i32, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp])):
         if hasattr(L, name):
             getattr(L, name).argtypes = at
     L.svo_build_terrain.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
@@ -655,6 +656,66 @@ class Tree:
                                              C.c_void_p(out.data_ptr()) if n else None, C.c_void_p(s) if s else None),
                "svo_tree_get_blocks_gpu")
         return out
+
+    def _list_box(self, origin, shape):
+        """(origin array or None, nx, ny, nz) of list_voxels' / count_voxels' box: both None is the whole extent"""
+        if origin is None and shape is None:
+            return None, 0, 0, 0
+        if origin is None or shape is None or len(origin) != 3 or len(shape) != 3:
+            raise ValueError("origin and shape: three integers each, or both None for the whole extent")
+        nz, ny, nx = (int(n) for n in shape)
+        return (C.c_int32 * 3)(*[int(v) for v in origin]), nx, ny, nz
+
+    def count_voxels(self, origin=None, shape=None):
+        """svo_tree_list_voxels_gpu without buffers: the number of voxels this (uploaded) tree stores in the box of `shape`
+        = (nz, ny, nx) at origin (x, y, z) — both None: the whole extent — as an int.  Uniform regions are counted in
+        closed form, never expanded; the box must lie inside the extent (no wrap)."""
+        if self.info().device < 0:
+            raise SvoError("svo_tree_list_voxels_gpu failed (-4): tree not uploaded (svo_upload)")
+        o, nx, ny, nz = self._list_box(origin, shape)
+        n = C.c_int64(-1)
+        _check(lib().svo_tree_list_voxels_gpu(self._h, o, nx, ny, nz, None, None, 0, C.byref(n), None), "svo_tree_list_voxels_gpu")
+        return n.value
+
+    def list_voxels(self, origin=None, shape=None, out=None, stream=None):
+        """svo_tree_list_voxels_gpu: the voxels this (uploaded) tree stores in the box of `shape` = (nz, ny, nx) at origin
+        (x, y, z) — both None: the whole extent — as (xyz, ids): an int32 CUDA tensor (n, 3) of positions and an int16 CUDA
+        tensor (n,) of palette ids (the bits are the ids), in the point builder's key order: points_gpu(levels,
+        *t.list_voxels(), t.palette(), view) rebuilds the tree.  out=(xyz, ids): caller tensors whose first dimension is
+        the capacity; views of their first n entries come back (SvoError -5 when the box holds more).  Without `out` the
+        voxels are counted first and the tensors allocated exactly.  Runs on `stream` and is complete on return."""
+        torch = _torch()
+        dev = self.info().device
+        if dev < 0:
+            raise SvoError("svo_tree_list_voxels_gpu failed (-4): tree not uploaded (svo_upload)")
+        o, nx, ny, nz = self._list_box(origin, shape)
+        s = getattr(stream, "cuda_stream", stream)
+        s = C.c_void_p(s) if s else None
+        f = lib().svo_tree_list_voxels_gpu
+        n = C.c_int64(-1)
+        if out is None:
+            _check(f(self._h, o, nx, ny, nz, None, None, 0, C.byref(n), s), "svo_tree_list_voxels_gpu")
+            # (a count no list can hold is allocated one entry: the library then says so)
+            cap = n.value if n.value <= 0x7FFFFFFF else 1
+            where = torch.device("cuda", dev)
+            xyz, ids = torch.empty((cap, 3), dtype=torch.int32, device=where), torch.empty((cap,), dtype=torch.int16, device=where)
+            if cap == 0:
+                return xyz, ids
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != 2 or not all(isinstance(x, torch.Tensor) for x in out):
+                raise ValueError("out: a pair (xyz, ids) of CUDA tensors")
+            xyz, ids = out
+            if (xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.dtype != torch.int32 or not xyz.is_cuda or xyz.device.index != dev
+                    or not xyz.is_contiguous()):
+                raise ValueError("out: xyz must be a contiguous int32 CUDA tensor of shape (cap, 3) on the tree's device")
+            if (tuple(ids.shape) != (xyz.shape[0],) or ids.dtype not in (torch.int16, torch.uint16) or not ids.is_cuda
+                    or ids.device.index != dev or not ids.is_contiguous()):
+                raise ValueError("out: ids must be a contiguous int16 CUDA tensor of shape (cap,) on the tree's device")
+            cap = int(xyz.shape[0])
+        # (a tensor without elements has no address to give: the library takes NULL buffers only with cap == 0)
+        px, pi = (C.c_void_p(xyz.data_ptr()), C.c_void_p(ids.data_ptr())) if cap else (None, None)
+        _check(f(self._h, o, nx, ny, nz, px, pi, cap, C.byref(n), s), "svo_tree_list_voxels_gpu")
+        return xyz[:n.value], ids[:n.value]
 
     def patch_volume(self, voxels, origin):
         """svo_tree_patch_volume_gpu: replace this (uploaded) tree's content inside a box by `voxels`, on the device.

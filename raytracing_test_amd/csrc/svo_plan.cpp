@@ -412,6 +412,26 @@ void patch_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, c
     *n_mats = s.n_mats;
 }
 
+int list_box(int32_t levels, const int32_t* origin, int32_t nx, int32_t ny, int32_t nz, ListBox* B) {
+    const int64_t E = (int64_t)1 << (2 * levels);
+    if (!origin) {
+        for (int a = 0; a < 3; a++) {
+            B->lo[a] = 0;
+            B->hi[a] = (int32_t)E;
+        }
+        return LIST_BOX_OK;
+    }
+    const int32_t dim[3] = {nx, ny, nz};
+    for (int a = 0; a < 3; a++)
+        if (dim[a] <= 0) return LIST_BOX_DIM;
+    for (int a = 0; a < 3; a++) {
+        if (origin[a] < 0 || (int64_t)origin[a] + dim[a] > E) return LIST_BOX_EXTENT;
+        B->lo[a] = origin[a];
+        B->hi[a] = origin[a] + dim[a];
+    }
+    return LIST_BOX_OK;
+}
+
 SchedPlan sched_decide(svo_tree::Sched& s, int64_t blocks, const int64_t sig[7], const float cam[6]) {
     if (s.blocks != blocks || !std::equal(sig, sig + 7, s.sig)) {
         s.blocks = blocks;

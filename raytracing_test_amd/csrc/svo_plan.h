@@ -5,6 +5,7 @@
 #include <utility>
 
 #include "svo_internal.h"
+#include "svo_list_unrank.h"
 
 namespace svo {
 
@@ -90,6 +91,13 @@ PatchAnchor points_anchor(const Node* nodes, int32_t levels, uint64_t key_first,
 // merged into column rectangles {x0, z0, x1, z1} in voxels for svo_tree.ceil_dirty: runs of adjacent blocks within a block
 // row, and runs of equal span in consecutive rows joined into one rectangle.  `blocks` is sorted in place.
 std::vector<std::array<int64_t, 4>> ceil_block_rects(std::vector<uint64_t>& blocks);
+
+// svo_tree_list_voxels_gpu (svo_list_voxels.hip) lists the voxels inside a box of the extent 4^levels: origin == NULL is the
+// whole extent (the dimensions are then ignored), otherwise origin >= 0, origin + n <= extent and positive dimensions, with
+// no wrap (the patch box's rule; the sums are taken in 64 bits).  Fills *B; LIST_BOX_DIM: a non-positive dimension;
+// LIST_BOX_EXTENT: the box leaves the extent.
+enum : int { LIST_BOX_OK = 0, LIST_BOX_DIM = 1, LIST_BOX_EXTENT = 2 };
+int list_box(int32_t levels, const int32_t* origin, int32_t nx, int32_t ny, int32_t nz, ListBox* B);
 
 // A schedule predicts a frame from the last one: a camera that turned more than kSchedTurn or moved more than kSchedMove
 // voxels since runs the default order (and re-primes).  Measured (tools/shade_motion.py, r04_ax): a still view 0.462 ->

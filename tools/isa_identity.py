@@ -1,9 +1,10 @@
 """Are the kernels of two builds the same instruction streams?
-usage: python tools/isa_identity.py DIR_A DIR_B   (directories of `hipcc <build.py HIP_FLAGS> --offload-device-only -S` output, *.s)
+usage: python tools/isa_identity.py [--max-name N] DIR_A DIR_B   (directories of `hipcc <build.py HIP_FLAGS> --offload-device-only -S` output, *.s)
 Each kernel is keyed by its demangled name without the `(anonymous namespace)::` qualifier; its text (label to end marker,
 comments dropped, local labels renamed by order of appearance) and its .amdhsa_ descriptor block are hashed together.
 Prints one line per kernel with the hash of each side and a final count; exits 1 unless both sides hold the same kernels
-with equal hashes."""
+with equal hashes.  --max-name N prints a name longer than N characters (hipCUB's template instances run to 2,800) as its
+first N characters, `...` and the hash of the whole name: the comparison is still by whole names."""
 import glob
 import hashlib
 import os
@@ -54,14 +55,23 @@ def digest(rec):
     return hashlib.sha256("\0".join(rec).encode()).hexdigest()[:16] if rec else "-"
 
 
+def short(key, limit):
+    if not limit or len(key) <= limit:
+        return key
+    return "%s...#%s" % (key[:limit], hashlib.sha256(key.encode()).hexdigest()[:12])
+
+
 def main():
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    args, limit = sys.argv[1:], 0
+    if args and args[0] == "--max-name":
+        limit, args = int(args[1]), args[2:]
+    a, b = kernels(args[0]), kernels(args[1])
     same = 0
     for key in sorted(set(a) | set(b)):
         ok = key in a and a[key] == b.get(key)
         same += ok
-        print("%-9s %-16s %-16s %s" % ("same" if ok else "DIFFERENT", digest(a.get(key)), digest(b.get(key)), key))
-    name = [os.path.basename(os.path.normpath(d)) for d in sys.argv[1:3]]
+        print("%-9s %-16s %-16s %s" % ("same" if ok else "DIFFERENT", digest(a.get(key)), digest(b.get(key)), short(key, limit)))
+    name = [os.path.basename(os.path.normpath(d)) for d in args[:2]]
     print("%d kernels in %s, %d in %s, %d identical" % (len(a), name[0], len(b), name[1], same))
     return 0 if same == len(a) == len(b) else 1
 

@@ -32,7 +32,7 @@ extern "C" {
                              svo_volume_classify_pass, svo_tree_patch_volume_gpu, svo_tree_garbage,
                              svo_tree_patch_times, svo_tree_compact_gpu, svo_tree_compact_times,
                              svo_build_points_gpu, svo_tree_get_blocks_gpu,
-                             svo_tree_patch_points_gpu, svo_tree_list_voxels_gpu */
+                             svo_tree_patch_points_gpu, svo_tree_list_voxels_gpu, svo_tree_diff_gpu */
 
 enum {
     SVO_OK = 0,
@@ -252,6 +252,37 @@ int svo_tree_get_blocks_gpu(const svo_tree* t, const int32_t* xyz, int64_t n, ui
    the device. */
 int svo_tree_list_voxels_gpu(const svo_tree* t, const int32_t origin[3], int32_t nx, int32_t ny, int32_t nz,
                              int32_t* xyz, uint16_t* ids, int64_t cap, int64_t* n, void* hip_stream);
+/* List the voxels in which two resident trees differ, on the device: the voxels of the box at which the id that `a` stores
+   differs from the id that `b` stores, written as (x, y, z, id_b) in svo_tree_list_voxels_gpu's buffer layout; id_b is 0
+   where b stores nothing.  Each tree is read in its own view, from its device copy.  The output is the edit list that
+   makes a into b: svo_tree_patch_points_gpu(a, xyz, ids, *n) leaves a's content in the box equal to b's (the ids are b's
+   numbers: the patch refuses ids at or beyond a's palette size).  Ids are compared as numbers; the palettes are NOT
+   compared, so the same number with different palette entries counts as equal.  The views may differ: a solid-view and a
+   full-view tree of one world differ exactly in the liquid voxels.  a == b is allowed and yields 0.
+   The box, the order, the count-only call, *n and the buffers follow svo_tree_list_voxels_gpu exactly: origin == NULL is the
+   whole extent, else origin >= 0, origin + n <= 4^levels, positive dimensions, no wrap; the output is strictly increasing
+   in the point builder's key and no sort takes place, so that the diff of an empty tree against t equals the listing of t
+   entry for entry; xyz == NULL && ids == NULL && cap == 0 writes nothing and returns the count; *n is a HOST value, the
+   exact 64-bit number of differing voxels, set on SVO_OK and on the capacity errors below.
+   Uniform regions are never expanded: two K_SOLID regions, or a K_SOLID region and an empty one, contribute the clipped
+   volume of the smaller region in closed form where their ids differ, and nothing, without being descended, where they
+   are equal (a solid 16384^3 root against an empty tree counts 2^42).  The two trees are walked side by side, one list of
+   pairs of regions per depth in the listing's four phases; a region uniform on both sides is never an item of a list, so
+   the items number at most the records reached in a plus those reached in b.  No position is looked up from a root.
+   Scratch in HBM, freed on return: 92 B per item (two 16-B record copies, 16 B for the region's first voxel, a 16-B
+   link to its children, 8 B each for its total and its offset, 4 + 8 B for a count and its scan, used twice; 84 B for a
+   count-only call), 36 B per uniform region written from, and hipCUB's scan temporaries.
+   Any uploaded trees of 1 to 7 levels, either view, however built, in every layout the patches leave.  Both trees are only
+   read: host images, ceilings, garbage counts and schedules stay as they are.
+   SVO_EINVAL: NULL a, b or n; one of xyz / ids NULL with the other set or with cap > 0; cap < 0; a non-positive dimension;
+   a box that leaves the extent; trees of different levels; trees on different devices (found after the upload check).
+   SVO_ESTATE: either tree is not uploaded.  SVO_ERANGE, with *n set and nothing written: the count exceeds 2^31 - 1 when
+   buffers are given, or the count exceeds cap.  SVO_ENOMEM: no scratch.  Arguments and state are checked before the first
+   HIP call; after any error the caller's buffers and both trees are untouched.
+   The call runs on hip_stream and waits for it before returning; it does not synchronise the device. */
+int svo_tree_diff_gpu(const svo_tree* a, const svo_tree* b,
+                      const int32_t origin[3], int32_t nx, int32_t ny, int32_t nz,
+                      int32_t* xyz, uint16_t* ids, int64_t cap, int64_t* n, void* hip_stream);
 /* Patch a resident tree from a dense box of voxels in HBM, on the device: after the call the tree's content inside the
    box is exactly `voxels` (ids the tree's view does not hold are stored empty, as in svo_build_volume_gpu); everything
    outside the box is as before.  Any uploaded tree (volume-, terrain- or world-built), either view, any size (nodes are

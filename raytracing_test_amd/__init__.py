@@ -171,6 +171,7 @@ ABI_SYMBOLS = (
     "svo_build_id", "svo_build_volume_gpu", "svo_tree_read_volume", "svo_volume_classify_pass",
     "svo_tree_patch_volume_gpu", "svo_tree_garbage", "svo_tree_patch_times", "svo_tree_compact_gpu", "svo_tree_compact_times",
     "svo_build_points_gpu", "svo_tree_get_blocks_gpu", "svo_tree_patch_points_gpu", "svo_tree_list_voxels_gpu",
+    "svo_tree_diff_gpu",
 )
 
 
@@ -259,7 +260,8 @@ def lib():
                      ("svo_build_points_gpu", [C.POINTER(PointsDesc), C.POINTER(vp)]),
                      ("svo_tree_get_blocks_gpu", [vp, vp, C.c_int64, vp, vp]),
                      ("svo_tree_patch_points_gpu", [vp, vp, vp, C.c_int64]),
-                     ("svo_tree_list_voxels_gpu", [vp, C.POINTER(i32), i32, i32, i32, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp])):
+                     ("svo_tree_list_voxels_gpu", [vp, C.POINTER(i32), i32, i32, i32, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
+                     ("svo_tree_diff_gpu", [vp, vp, C.POINTER(i32), i32, i32, i32, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp])):
         if hasattr(L, name):
             getattr(L, name).argtypes = at
     L.svo_build_terrain.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
@@ -677,24 +679,16 @@ class Tree:
         _check(lib().svo_tree_list_voxels_gpu(self._h, o, nx, ny, nz, None, None, 0, C.byref(n), None), "svo_tree_list_voxels_gpu")
         return n.value
 
-    def list_voxels(self, origin=None, shape=None, out=None, stream=None):
-        """svo_tree_list_voxels_gpu: the voxels this (uploaded) tree stores in the box of `shape` = (nz, ny, nx) at origin
-        (x, y, z) — both None: the whole extent — as (xyz, ids): an int32 CUDA tensor (n, 3) of positions and an int16 CUDA
-        tensor (n,) of palette ids (the bits are the ids), in the point builder's key order: points_gpu(levels,
-        *t.list_voxels(), t.palette(), view) rebuilds the tree.  out=(xyz, ids): caller tensors whose first dimension is
-        the capacity; views of their first n entries come back (SvoError -5 when the box holds more).  Without `out` the
-        voxels are counted first and the tensors allocated exactly.  Runs on `stream` and is complete on return."""
+    def _list_into(self, name, call, dev, out, stream):
+        """the buffer protocol svo_tree_list_voxels_gpu and svo_tree_diff_gpu share: call(xyz, ids, cap, n, stream) is the
+        entry point `name` with its leading arguments bound.  Without `out` a count-only call, then exact-size tensors;
+        with out=(xyz, ids) the caller's tensors, validated.  Returns views of the first n entries."""
         torch = _torch()
-        dev = self.info().device
-        if dev < 0:
-            raise SvoError("svo_tree_list_voxels_gpu failed (-4): tree not uploaded (svo_upload)")
-        o, nx, ny, nz = self._list_box(origin, shape)
         s = getattr(stream, "cuda_stream", stream)
         s = C.c_void_p(s) if s else None
-        f = lib().svo_tree_list_voxels_gpu
         n = C.c_int64(-1)
         if out is None:
-            _check(f(self._h, o, nx, ny, nz, None, None, 0, C.byref(n), s), "svo_tree_list_voxels_gpu")
+            _check(call(None, None, 0, C.byref(n), s), name)
             # (a count no list can hold is allocated one entry: the library then says so)
             cap = n.value if n.value <= 0x7FFFFFFF else 1
             where = torch.device("cuda", dev)
@@ -714,8 +708,52 @@ class Tree:
             cap = int(xyz.shape[0])
         # (a tensor without elements has no address to give: the library takes NULL buffers only with cap == 0)
         px, pi = (C.c_void_p(xyz.data_ptr()), C.c_void_p(ids.data_ptr())) if cap else (None, None)
-        _check(f(self._h, o, nx, ny, nz, px, pi, cap, C.byref(n), s), "svo_tree_list_voxels_gpu")
+        _check(call(px, pi, cap, C.byref(n), s), name)
         return xyz[:n.value], ids[:n.value]
+
+    def list_voxels(self, origin=None, shape=None, out=None, stream=None):
+        """svo_tree_list_voxels_gpu: the voxels this (uploaded) tree stores in the box of `shape` = (nz, ny, nx) at origin
+        (x, y, z) — both None: the whole extent — as (xyz, ids): an int32 CUDA tensor (n, 3) of positions and an int16 CUDA
+        tensor (n,) of palette ids (the bits are the ids), in the point builder's key order: points_gpu(levels,
+        *t.list_voxels(), t.palette(), view) rebuilds the tree.  out=(xyz, ids): caller tensors whose first dimension is
+        the capacity; views of their first n entries come back (SvoError -5 when the box holds more).  Without `out` the
+        voxels are counted first and the tensors allocated exactly.  Runs on `stream` and is complete on return."""
+        dev = self.info().device
+        if dev < 0:
+            raise SvoError("svo_tree_list_voxels_gpu failed (-4): tree not uploaded (svo_upload)")
+        o, nx, ny, nz = self._list_box(origin, shape)
+        f = lib().svo_tree_list_voxels_gpu
+        return self._list_into("svo_tree_list_voxels_gpu", lambda *rest: f(self._h, o, nx, ny, nz, *rest), dev, out, stream)
+
+    def _diff_device(self, other):
+        """the device of this tree for a diff against `other`: both must be uploaded (as the library would say)"""
+        if not isinstance(other, Tree):
+            raise ValueError("other: a Tree")
+        dev = self.info().device
+        for name, d in (("a", dev), ("b", other.info().device)):
+            if d < 0:
+                raise SvoError("svo_tree_diff_gpu failed (-4): tree %s not uploaded (svo_upload)" % name)
+        return dev
+
+    def count_diff(self, other, origin=None, shape=None):
+        """svo_tree_diff_gpu without buffers: the number of voxels of the box of `shape` = (nz, ny, nx) at origin (x, y, z)
+        — both None: the whole extent — at which this (uploaded) tree and `other` store different ids, as an int.  Regions
+        uniform on both sides are counted in closed form, never expanded; the trees must have equal levels."""
+        self._diff_device(other)
+        o, nx, ny, nz = self._list_box(origin, shape)
+        n = C.c_int64(-1)
+        _check(lib().svo_tree_diff_gpu(self._h, other._h, o, nx, ny, nz, None, None, 0, C.byref(n), None), "svo_tree_diff_gpu")
+        return n.value
+
+    def diff_voxels(self, other, origin=None, shape=None, out=None, stream=None):
+        """svo_tree_diff_gpu: the voxels of the box (as in list_voxels) at which this (uploaded) tree and `other` store
+        different ids, as (xyz, ids) in list_voxels' form and key order, ids being `other`'s (0 where it stores nothing):
+        self.patch_points(*self.diff_voxels(other)) gives this tree other's content.  Ids are compared as numbers, the
+        palettes are not compared.  out, stream: as for list_voxels."""
+        dev = self._diff_device(other)
+        o, nx, ny, nz = self._list_box(origin, shape)
+        f = lib().svo_tree_diff_gpu
+        return self._list_into("svo_tree_diff_gpu", lambda *rest: f(self._h, other._h, o, nx, ny, nz, *rest), dev, out, stream)
 
     def patch_volume(self, voxels, origin):
         """svo_tree_patch_volume_gpu: replace this (uploaded) tree's content inside a box by `voxels`, on the device.

@@ -32,7 +32,8 @@ extern "C" {
                              svo_volume_classify_pass, svo_tree_patch_volume_gpu, svo_tree_garbage,
                              svo_tree_patch_times, svo_tree_compact_gpu, svo_tree_compact_times,
                              svo_build_points_gpu, svo_tree_get_blocks_gpu,
-                             svo_tree_patch_points_gpu, svo_tree_list_voxels_gpu, svo_tree_diff_gpu */
+                             svo_tree_patch_points_gpu, svo_tree_list_voxels_gpu, svo_tree_diff_gpu,
+                             svo_tree_patch_shapes_gpu */
 
 enum {
     SVO_OK = 0,
@@ -342,13 +343,62 @@ int svo_tree_patch_volume_gpu(svo_tree* t, const svo_volume_box* box);
    The device is synchronised on entry (the list may come from any stream, and records and ceilings are rewritten in
    place: call it between frames); it runs on the null stream and the call is complete on return. */
 int svo_tree_patch_points_gpu(svo_tree* t, const int32_t* xyz, const uint16_t* ids, int64_t n);
+/* Patch a resident tree from a list of solid shapes — boxes and balls, each with the id it stores — on the device, at a
+   cost that follows the shapes' surfaces and never their volumes: filling 1300^3 voxels of a 16384^3 world appends at
+   most 64 records per aligned cell the box cuts (about two million, 32 MB), where a dense box would hold 4.4 GB and an
+   edit list 2.2 * 10^9 entries, more than svo_tree_patch_points_gpu takes.  `shapes` is a HOST
+   array of n shapes, applied in list order as svo_tree_patch_points_gpu's entries are: after the call a voxel holds the
+   id of the last shape that contains it and a voxel inside no shape is as before.  Id 0 erases; an id the tree's view
+   does not hold is stored empty (the other patches' rule, resolved per shape on the host).  Ids are the tree's own
+   palette: there is no palette growth.  A box must lie within the extent (the patch box's rule); a ball is clipped to it,
+   so its centre may lie outside.
+   Any uploaded tree (world-, terrain-, volume- or points-built, patched or not), either view, every layout the patches
+   leave, any size (every node and material index is widened to 64 bits before it addresses memory).  The descent is
+   svo_tree_patch_volume_gpu's, with the box's class pyramid replaced by a closed form: an aligned cell no shape touches
+   keeps its record and subtree; a cell wholly inside the deciding shape becomes one K_SOLID record at whatever level it
+   sits (for id 0: a clear slot bit); a cell the deciding shape cuts is re-emitted one level down, in new child blocks
+   appended to the arrays, down to bricks classified from their 64 composite voxels.  The shape that decides a cell is
+   the last in the list that meets it; a cell cut by a late shape and covered by an earlier one therefore descends to
+   bricks that come out uniform.  As after the other patches the result is the tree's content, not its canonical layout
+   (records with mask 0 may result, full one-material bricks may stay bricks; svo_tree_compact_gpu restores the layout);
+   no K_BRICK record with mask 0 exists.  Only one record is rewritten in place: that of the deepest interior node whose
+   region holds every shape's clipped bounding box (the anchor).  The arrays restart — the tree becomes a lone K_SOLID
+   root, or the lone empty root for id 0, and nothing stays superseded — only when the last shape that meets the extent
+   covers all of it; a bounding box equal to the extent does not restart them.
+   The device arrays are reallocated (with the slack of a fresh upload) only when the appended tail would not fit; the
+   host image, the column ceilings (exact, over one rectangle per shape's clipped column footprint), the tree's top row
+   and svo_tree_garbage's counts are brought up to date.  A world-built tree patched this way no longer follows its
+   svo_world: svo_tree_update on it returns SVO_ESTATE.
+   Scratch in HBM, freed on return: 40 B per shape, 24 + 24 B per cut cell and level (its work item and four scan words), 16 B per appended record.  Every
+   cell is asked against every shape: there is no spatial index over the list, so the time is (cut cells) x n.
+   All errors are found on the host before the first HIP call, and after any error the tree and its counts are unchanged.
+   SVO_EINVAL: NULL tree, NULL shapes with n > 0, n < 0, an unknown kind, a box with a non-positive dimension or one
+   that leaves the extent, r2 < 0.  SVO_ERANGE: n > 1024; a ball centre with |c| > 2^20 on an axis or r2 > 2^42 (within
+   these limits every distance sum is exact in int64); an id >= the tree's palette size; a tree of one level; arrays that
+   would pass 2^32 elements (found once the totals are known, before the tree is touched).  The first shape that fails
+   decides, and the message gives its index.  SVO_ESTATE: the tree is not uploaded, or has host edits not yet synced
+   (svo_tree_sync); it is checked after the arguments.  SVO_ENOMEM: no scratch.  n == 0, or every shape clipped away,
+   returns SVO_OK after these checks without device work.
+   The device is synchronised on entry (records and ceilings are rewritten in place: call it between frames); it runs on
+   the null stream and the call is complete on return.  svo_tree_patch_times reports it. */
+#define SVO_SHAPE_BOX 0  /* voxels a <= p < a + b; b positive; must lie within the extent (the patch box's rule) */
+#define SVO_SHAPE_BALL 1 /* voxels with |p - a|^2 <= r2 in exact integers; clipped to the extent; b ignored */
+typedef struct {
+    int32_t kind;  /* SVO_SHAPE_BOX / SVO_SHAPE_BALL */
+    int32_t a[3];  /* box: its first voxel; ball: its centre */
+    int32_t b[3];  /* box: its dimensions (x, y, z) */
+    int64_t r2;    /* ball: the squared radius, 0 .. 2^42 */
+    uint16_t id;   /* the tree's own palette id the shape's voxels store, 0 = erase */
+} svo_shape;
+int svo_tree_patch_shapes_gpu(svo_tree* t, const svo_shape* shapes /* HOST */, int32_t n);
 /* node records and material entries superseded by edits (svo_tree_update, svo_tree_patch_volume_gpu,
-   svo_tree_patch_points_gpu) since the last full build: still in the arrays, no longer reachable (either may be NULL) */
+   svo_tree_patch_points_gpu, svo_tree_patch_shapes_gpu) since the last full build: still in the arrays, no longer reachable (either may be NULL) */
 int svo_tree_garbage(const svo_tree* t, uint64_t* nodes, uint64_t* mats);
 /* diagnostics (tools/volume_patch_timing.py, tools/points_patch_timing.py): host-clock milliseconds of the tree's last
-   svo_tree_patch_volume_gpu or svo_tree_patch_points_gpu, whichever ran last, after its entry synchronisation: ms[0] the
-   device passes (volume: pyramid, count and write passes into scratch; points: keys, sort, edit list, column blocks, count
-   and write passes), ms[1] the commit to the arrays and the copy back to the host image, ms[2] the host's ceiling update
+   svo_tree_patch_volume_gpu, svo_tree_patch_points_gpu or svo_tree_patch_shapes_gpu, whichever ran last, after its entry
+   synchronisation: ms[0] the device passes (volume: pyramid, count and write passes into scratch; points: keys, sort, edit
+   list, column blocks, count and write passes; shapes: the table's upload, the host's garbage walk, count and write
+   passes), ms[1] the commit to the arrays and the copy back to the host image, ms[2] the host's ceiling update
    (with the tree's top row) */
 int svo_tree_patch_times(const svo_tree* t, double ms[3]);
 /* Re-emit an uploaded tree, on its device, as the canonical linearisation of its own content: after the call the node

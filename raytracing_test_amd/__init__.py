@@ -139,6 +139,42 @@ class PointsDesc(C.Structure):
                 ("n_palette", C.c_uint32), ("view", C.c_int32), ("device", C.c_int32)]
 
 
+SHAPE_BOX, SHAPE_BALL = 0, 1
+
+
+class Shape(C.Structure):
+    """svo_shape: a solid box (a = first voxel, b = dimensions) or ball (a = centre, r2 = squared radius) and the palette id
+    its voxels store (0 erases); see box() and ball()"""
+
+    _fields_ = [("kind", C.c_int32), ("a", C.c_int32 * 3), ("b", C.c_int32 * 3), ("r2", C.c_int64), ("id", C.c_uint16)]
+
+
+def box(origin, dims, id):
+    """The Shape of the voxels origin <= p < origin + dims, (x, y, z) each, storing palette id `id` (0 erases): for
+    Tree.patch_shapes.  The box must lie within the tree's extent."""
+    if len(origin) != 3 or len(dims) != 3:
+        raise ValueError("origin and dims: three integers each")
+    s = Shape()
+    s.kind = SHAPE_BOX
+    s.a[:] = [int(v) for v in origin]
+    s.b[:] = [int(v) for v in dims]
+    s.id = int(id)
+    return s
+
+
+def ball(centre, r2, id):
+    """The Shape of the voxels p with |p - centre|^2 <= r2 (exact integers; r2 is the squared radius), storing palette id
+    `id` (0 erases): for Tree.patch_shapes.  The ball is clipped to the tree's extent; its centre may lie outside."""
+    if len(centre) != 3:
+        raise ValueError("centre: three integers")
+    s = Shape()
+    s.kind = SHAPE_BALL
+    s.a[:] = [int(v) for v in centre]
+    s.r2 = int(r2)
+    s.id = int(id)
+    return s
+
+
 class Hits(C.Structure):
     _fields_ = [("pos_steps", C.c_void_p), ("t", C.c_void_p), ("info", C.c_void_p), ("ao", C.c_void_p)]
 
@@ -171,7 +207,7 @@ ABI_SYMBOLS = (
     "svo_build_id", "svo_build_volume_gpu", "svo_tree_read_volume", "svo_volume_classify_pass",
     "svo_tree_patch_volume_gpu", "svo_tree_garbage", "svo_tree_patch_times", "svo_tree_compact_gpu", "svo_tree_compact_times",
     "svo_build_points_gpu", "svo_tree_get_blocks_gpu", "svo_tree_patch_points_gpu", "svo_tree_list_voxels_gpu",
-    "svo_tree_diff_gpu",
+    "svo_tree_diff_gpu", "svo_tree_patch_shapes_gpu",
 )
 
 
@@ -261,7 +297,8 @@ def lib():
                      ("svo_tree_get_blocks_gpu", [vp, vp, C.c_int64, vp, vp]),
                      ("svo_tree_patch_points_gpu", [vp, vp, vp, C.c_int64]),
                      ("svo_tree_list_voxels_gpu", [vp, C.POINTER(i32), i32, i32, i32, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
-                     ("svo_tree_diff_gpu", [vp, vp, C.POINTER(i32), i32, i32, i32, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp])):
+                     ("svo_tree_diff_gpu", [vp, vp, C.POINTER(i32), i32, i32, i32, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
+                     ("svo_tree_patch_shapes_gpu", [vp, C.POINTER(Shape), i32])):
         if hasattr(L, name):
             getattr(L, name).argtypes = at
     L.svo_build_terrain.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
@@ -797,15 +834,32 @@ class Tree:
         del xyz, ids
         return self
 
+    def patch_shapes(self, shapes):
+        """svo_tree_patch_shapes_gpu: apply a list of solid shapes — box(origin, dims, id) and ball(centre, r2, id) — to
+        this (uploaded) tree, on the device, in list order: afterwards a voxel holds the id of the last shape that
+        contains it (id 0 erases, an id the tree's view does not store becomes empty) and a voxel inside no shape is as
+        it was.  The cost follows the shapes' surfaces, not their volumes: a cell wholly inside a shape is one record.
+        The host image, the ceilings and garbage() are brought up to date, and the call is complete on return.  Any
+        uploaded tree may be patched; a World-built one no longer follows its World afterwards (update() then fails)."""
+        if self.info().device < 0:
+            raise SvoError("svo_tree_patch_shapes_gpu failed (-4): tree not uploaded (svo_upload)")
+        shapes = list(shapes)
+        if not all(isinstance(s, Shape) for s in shapes):
+            raise ValueError("shapes: Shape objects, as box() and ball() make them")
+        arr = (Shape * max(1, len(shapes)))(*shapes)
+        _check(lib().svo_tree_patch_shapes_gpu(self._h, arr if shapes else None, len(shapes)), "svo_tree_patch_shapes_gpu")
+        return self
+
     def garbage(self):
-        """svo_tree_garbage: (node records, material entries) superseded by update() / patch_volume() / patch_points() since the last
+        """svo_tree_garbage: (node records, material entries) superseded by update() / patch_volume() / patch_points() /
+        patch_shapes() since the last
         full build or compact(): when they outweigh the tree, compact() pays"""
         n, m = C.c_uint64(), C.c_uint64()
         _check(lib().svo_tree_garbage(self._h, C.byref(n), C.byref(m)), "svo_tree_garbage")
         return n.value, m.value
 
     def patch_times(self):
-        """svo_tree_patch_times: host-clock ms of the last patch_volume() or patch_points() — (device passes, commit + host
+        """svo_tree_patch_times: host-clock ms of the last patch_volume(), patch_points() or patch_shapes() — (device passes, commit + host
         image, ceilings)"""
         ms = (C.c_double * 3)()
         _check(lib().svo_tree_patch_times(self._h, ms), "svo_tree_patch_times")

@@ -412,6 +412,108 @@ void patch_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, c
     *n_mats = s.n_mats;
 }
 
+// floor(sqrt(v)) for 0 <= v <= 2^42: the double root, put right by at most one either way
+static int64_t isqrt_floor(int64_t v) {
+    int64_t r = (int64_t)__builtin_sqrt((double)v);
+    while (r > 0 && r * r > v) r--;
+    while ((r + 1) * (r + 1) <= v) r++;
+    return r;
+}
+
+int shapes_plan(int32_t levels, int32_t view, const std::vector<Material>& palette, const svo_shape* shapes, int32_t n, ShapesPlan* plan,
+                int32_t* bad) {
+    const int64_t E = (int64_t)1 << (2 * levels);
+    plan->table.clear();
+    plan->rects.clear();
+    for (int a = 0; a < 3; a++) {
+        plan->lo[a] = (int32_t)E;
+        plan->hi[a] = 0;
+    }
+    for (int32_t i = 0; i < n; i++) {
+        const svo_shape& s = shapes[i];
+        *bad = i;
+        int64_t lo[3], hi[3];
+        if (s.kind == SVO_SHAPE_BOX) {
+            for (int a = 0; a < 3; a++)
+                if (s.b[a] <= 0) return SHAPES_BOX_DIM;
+            for (int a = 0; a < 3; a++) {
+                if (s.a[a] < 0 || (int64_t)s.a[a] + s.b[a] > E) return SHAPES_BOX_EXTENT;
+                lo[a] = s.a[a];
+                hi[a] = (int64_t)s.a[a] + s.b[a];
+            }
+        } else if (s.kind == SVO_SHAPE_BALL) {
+            if (s.r2 < 0) return SHAPES_R2_NEG;
+            for (int a = 0; a < 3; a++)
+                if (s.a[a] > kShapeCentreMax || s.a[a] < -kShapeCentreMax) return SHAPES_CENTRE;
+            if (s.r2 > kShapeR2Max) return SHAPES_R2_BIG;
+            const int64_t r = isqrt_floor(s.r2);
+            for (int a = 0; a < 3; a++) {
+                lo[a] = std::max<int64_t>(0, (int64_t)s.a[a] - r);
+                hi[a] = std::min<int64_t>(E, (int64_t)s.a[a] + r + 1);
+            }
+        } else {
+            return SHAPES_KIND;
+        }
+        if ((size_t)s.id >= palette.size()) return SHAPES_ID;
+        if (lo[0] >= hi[0] || lo[1] >= hi[1] || lo[2] >= hi[2]) continue;  // clipped away
+        ShapeRec r{s.kind == SVO_SHAPE_BOX ? kShapeBox : kShapeBall, {s.a[0], s.a[1], s.a[2]}, {0, 0, 0}, 0u, 0};
+        if (s.kind == SVO_SHAPE_BOX)
+            for (int a = 0; a < 3; a++) r.b[a] = (int32_t)hi[a];
+        else r.r2 = s.r2;
+        r.id = s.id != 0 && material_in_view(palette[s.id], view) ? (uint32_t)s.id : 0u;
+        plan->table.push_back(r);
+        plan->rects.push_back({lo[0], lo[2], hi[0], hi[2]});
+        for (int a = 0; a < 3; a++) {
+            plan->lo[a] = std::min(plan->lo[a], (int32_t)lo[a]);
+            plan->hi[a] = std::max(plan->hi[a], (int32_t)hi[a]);
+        }
+    }
+    *bad = -1;
+    return SHAPES_OK;
+}
+
+namespace {
+struct ShapesSuperseded {
+    const Node* nodes;
+    int32_t levels;
+    const ShapeRec* shapes;
+    int32_t n;
+    uint64_t n_nodes = 0, n_mats = 0;
+    // node ni's record is replaced: what hangs below it.  all: the cell lies wholly inside the deciding shape
+    void walk(uint32_t ni, const int32_t o[3], int depth, bool all) {
+        const Node& nd = nodes[ni];
+        const uint32_t kind = node_kind(nd.info);
+        if (kind == K_SOLID) return;
+        if (kind == K_BRICK) {
+            if (!(nd.info & K_UNIFORM)) n_mats += (uint64_t)__builtin_popcountll(nd.mask);
+            return;
+        }
+        n_nodes += (uint64_t)__builtin_popcountll(nd.mask);
+        const int32_t cs = 1 << (2 * (levels - 1 - depth));
+        uint64_t m = nd.mask;
+        uint32_t ci = nd.ref;
+        while (m) {
+            const uint32_t sl = (uint32_t)__builtin_ctzll(m);
+            m &= m - 1;
+            const uint32_t c = ci++;
+            const int32_t co[3] = {o[0] + (int32_t)(sl & 3u) * cs, o[1] + (int32_t)((sl >> 2) & 3u) * cs, o[2] + (int32_t)(sl >> 4) * cs};
+            uint32_t id;
+            const uint32_t rel = all ? (uint32_t)SHAPE_IN : cell_relation(shapes, n, co[0], co[1], co[2], cs, &id);
+            if (rel == SHAPE_IN) walk(c, co, depth + 1, true);
+            else if (rel == SHAPE_CUT) walk(c, co, depth + 1, false);  // (no shape touches it: the copied record keeps its subtree)
+        }
+    }
+};
+}  // namespace
+
+void shapes_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const ShapeRec* shapes, int32_t n, uint64_t* n_nodes,
+                       uint64_t* n_mats) {
+    ShapesSuperseded s{nodes, levels, shapes, n};
+    s.walk(a.node, a.o, a.depth, false);
+    *n_nodes = s.n_nodes;
+    *n_mats = s.n_mats;
+}
+
 int list_box(int32_t levels, const int32_t* origin, int32_t nx, int32_t ny, int32_t nz, ListBox* B) {
     const int64_t E = (int64_t)1 << (2 * levels);
     if (!origin) {

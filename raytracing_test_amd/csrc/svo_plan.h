@@ -6,6 +6,7 @@
 
 #include "svo_internal.h"
 #include "svo_list_unrank.h"
+#include "svo_shape_cell.h"
 
 namespace svo {
 
@@ -91,6 +92,36 @@ PatchAnchor points_anchor(const Node* nodes, int32_t levels, uint64_t key_first,
 // merged into column rectangles {x0, z0, x1, z1} in voxels for svo_tree.ceil_dirty: runs of adjacent blocks within a block
 // row, and runs of equal span in consecutive rows joined into one rectangle.  `blocks` is sorted in place.
 std::vector<std::array<int64_t, 4>> ceil_block_rects(std::vector<uint64_t>& blocks);
+
+// svo_tree_patch_shapes_gpu (svo_patch_shapes.hip) applies an ordered list of boxes and balls.  The host's part of it:
+// every shape checked (the first one that fails decides, *bad = its index), its id resolved against the tree's view
+// (an id the view does not hold is stored as 0) and its bounding box clipped to the extent 4^levels.  A shape whose
+// clipped box is empty is dropped; the others make up the table the cells are asked against (svo_shape_cell.h), one
+// column rectangle {x0, z0, x1, z1} each for svo_tree.ceil_dirty, and the union [lo, hi) of their boxes.
+enum : int {
+    SHAPES_OK = 0,
+    SHAPES_KIND = 1,        // an unknown kind
+    SHAPES_BOX_DIM = 2,     // a box with a non-positive dimension
+    SHAPES_BOX_EXTENT = 3,  // a box that leaves the extent
+    SHAPES_R2_NEG = 4,      // r2 < 0
+    SHAPES_CENTRE = 5,      // a ball centre beyond 2^20
+    SHAPES_R2_BIG = 6,      // r2 > 2^42
+    SHAPES_ID = 7,          // an id at or beyond the palette size
+};
+constexpr int32_t kShapesMax = 1024, kShapeCentreMax = 1 << 20;
+constexpr int64_t kShapeR2Max = (int64_t)1 << 42;
+struct ShapesPlan {
+    std::vector<ShapeRec> table;
+    std::vector<std::array<int64_t, 4>> rects;
+    int32_t lo[3], hi[3];
+};
+int shapes_plan(int32_t levels, int32_t view, const std::vector<Material>& palette, const svo_shape* shapes, int32_t n, ShapesPlan* plan,
+                int32_t* bad);
+// the analogue of patch_superseded: the node records and material entries the shapes patch supersedes below the anchor,
+// by the device pass's own rule — the child block of the anchor and of every interior node whose cell cell_relation calls
+// CUT, every subtree whose cell it calls IN, the material run of every brick whose cell is IN or CUT
+void shapes_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const ShapeRec* shapes, int32_t n, uint64_t* n_nodes,
+                       uint64_t* n_mats);
 
 // svo_tree_list_voxels_gpu (svo_list_voxels.hip) lists the voxels inside a box of the extent 4^levels: origin == NULL is the
 // whole extent (the dimensions are then ignored), otherwise origin >= 0, origin + n <= extent and positive dimensions, with

@@ -33,7 +33,7 @@ extern "C" {
                              svo_tree_patch_times, svo_tree_compact_gpu, svo_tree_compact_times,
                              svo_build_points_gpu, svo_tree_get_blocks_gpu,
                              svo_tree_patch_points_gpu, svo_tree_list_voxels_gpu, svo_tree_diff_gpu,
-                             svo_tree_patch_shapes_gpu */
+                             svo_tree_patch_shapes_gpu, svo_tree_patch_tree_gpu */
 
 enum {
     SVO_OK = 0,
@@ -391,14 +391,64 @@ typedef struct {
     uint16_t id;   /* the tree's own palette id the shape's voxels store, 0 = erase */
 } svo_shape;
 int svo_tree_patch_shapes_gpu(svo_tree* t, const svo_shape* shapes /* HOST */, int32_t n);
+/* Paste a box of one resident tree (src) into another (dst), on the device, without going through the voxels: copy,
+   paste, move and stamp for prefabs, regions of a world and snapshots.  For every voxel p of the box, q = dst_origin + p
+   and s = src(src_origin + p), read from src's device copy in src's own view (a voxel src does not store reads as 0).
+   SVO_PASTE_REPLACE: q takes s.  SVO_PASTE_KEEP_EMPTY: q takes s where s != 0 and is unchanged elsewhere (a prefab's air
+   is transparent).  The mode is decided on src's id first; only then is the id resolved against dst's view: an id dst's
+   view does not hold is stored empty (the other patches' rule), so pasting into the solid-view tree and into the
+   full-view tree of one world leaves them the two views of one pasted world.  Every voxel outside the destination box is
+   as before.  Ids are numbers in dst's palette and the palettes are not compared (svo_tree_diff_gpu's rule); there is no
+   palette growth.
+   src_origin == NULL means src's whole extent (nx, ny, nz are then ignored).  Both boxes must lie within their tree's
+   extent, with positive dimensions and no wrap.  The trees may have different levels: src 1 to 7, dst at least 2 (the
+   patches' rule).  The offset dst_origin - src_origin is arbitrary: it need not be a multiple of 4.  src == dst is
+   allowed and the boxes may overlap: everything is read from the arrays as they were on entry and written to scratch
+   first, as in every patch, so a self-paste copies the old content, never half-pasted content.  src is only ever read.
+   The descent is svo_tree_patch_shapes_gpu's, asked per aligned destination cell how it stands to src: the cell is
+   clipped to the box and shifted into src, where it meets at most 2 x 2 x 2 aligned src cells of its own width, each
+   found by a walk from src's root (a K_SOLID record at or above it: uniform; a clear slot bit at or above it: empty; a
+   record at its own level: mixed).  A cell outside the box, or (KEEP_EMPTY) over nothing src stores, keeps its record and
+   subtree; a cell wholly inside the box over src cells of one id becomes one K_SOLID record at whatever level it sits
+   (for id 0: a clear slot bit); every other cell is re-emitted one level down, in new child blocks appended to the arrays,
+   down to bricks classified from their 64 composite voxels.  The answer is conservative: a mixed src cell whose
+   overlapping part happens to be uniform descends and comes out right below, and a full one-material brick that stayed a
+   brick or an interior record with mask 0 in src counts as mixed.  A cell is cut only where the box's surface cuts it or
+   a src record of its level overlaps it, so the work follows the box's surface plus at most 8 destination cells per src
+   record reached in the box, never the volume: a 1300^3 K_SOLID region pastes at the cost of its faces.
+   As after the other patches the result is dst's content, not its canonical layout (records with mask 0 may result, full
+   one-material bricks may stay bricks; svo_tree_compact_gpu restores the layout); no K_BRICK record with mask 0 exists.
+   Only one record is rewritten in place: that of the deepest interior node whose region holds the destination box (the
+   anchor).  A REPLACE paste whose destination box is the whole extent restarts the arrays and nothing stays superseded
+   (the volume patch's rule; with src == dst too: the scratch is complete before the commit); KEEP_EMPTY never restarts.
+   The device arrays are reallocated (with the slack of a fresh upload) only when the appended tail would not fit; the
+   host image, the column ceilings (exact, over the destination box's column footprint), the tree's top row and
+   svo_tree_garbage's counts are brought up to date.  A world-built dst no longer follows its svo_world: svo_tree_update
+   on it returns SVO_ESTATE.
+   Scratch in HBM, freed on return: 4 B per 32 palette entries, 24 + 24 B per cut cell and level, 16 B per appended record.
+   All errors below but the last two are found on the host before the first HIP call: arguments first, then state, then
+   the anchor.  After any error both trees and dst's garbage counts are unchanged on host and device.
+   SVO_EINVAL: NULL dst, src or dst_origin; unknown flag bits; a non-positive dimension; either box leaving its extent.
+   SVO_ERANGE: a dst of one level; src's palette holds more entries than dst's (so no id can be out of range on the
+   device); arrays that would pass 2^32 elements (found once the totals are known, before dst is touched).
+   SVO_ESTATE: either tree is not uploaded, the trees are on different devices, or either has host edits not yet synced
+   (svo_tree_sync).  SVO_ENOMEM: no scratch.
+   The device is synchronised on entry (records and ceilings are rewritten in place: call it between frames); it runs on
+   the null stream and the call is complete on return.  svo_tree_patch_times reports it.
+   Not done here: palette merging or id remapping, rotation or mirroring, lists of placements in one call. */
+#define SVO_PASTE_REPLACE 0     /* the box of dst becomes the box of src, empties included */
+#define SVO_PASTE_KEEP_EMPTY 1  /* voxels at which src stores nothing leave dst as it is (a prefab's air is transparent) */
+int svo_tree_patch_tree_gpu(svo_tree* dst, const svo_tree* src,
+                            const int32_t src_origin[3], int32_t nx, int32_t ny, int32_t nz,
+                            const int32_t dst_origin[3], uint32_t flags);
 /* node records and material entries superseded by edits (svo_tree_update, svo_tree_patch_volume_gpu,
-   svo_tree_patch_points_gpu, svo_tree_patch_shapes_gpu) since the last full build: still in the arrays, no longer reachable (either may be NULL) */
+   svo_tree_patch_points_gpu, svo_tree_patch_shapes_gpu, svo_tree_patch_tree_gpu) since the last full build: still in the arrays, no longer reachable (either may be NULL) */
 int svo_tree_garbage(const svo_tree* t, uint64_t* nodes, uint64_t* mats);
 /* diagnostics (tools/volume_patch_timing.py, tools/points_patch_timing.py): host-clock milliseconds of the tree's last
-   svo_tree_patch_volume_gpu, svo_tree_patch_points_gpu or svo_tree_patch_shapes_gpu, whichever ran last, after its entry
+   svo_tree_patch_volume_gpu, svo_tree_patch_points_gpu, svo_tree_patch_shapes_gpu or svo_tree_patch_tree_gpu, whichever ran last, after its entry
    synchronisation: ms[0] the device passes (volume: pyramid, count and write passes into scratch; points: keys, sort, edit
-   list, column blocks, count and write passes; shapes: the table's upload, the host's garbage walk, count and write
-   passes), ms[1] the commit to the arrays and the copy back to the host image, ms[2] the host's ceiling update
+   list, column blocks, count and write passes; shapes and tree: the table's upload, the host's garbage walk, count and
+   write passes), ms[1] the commit to the arrays and the copy back to the host image, ms[2] the host's ceiling update
    (with the tree's top row) */
 int svo_tree_patch_times(const svo_tree* t, double ms[3]);
 /* Re-emit an uploaded tree, on its device, as the canonical linearisation of its own content: after the call the node

@@ -140,6 +140,7 @@ class PointsDesc(C.Structure):
 
 
 SHAPE_BOX, SHAPE_BALL = 0, 1
+PASTE_REPLACE, PASTE_KEEP_EMPTY = 0, 1   # svo_tree_patch_tree_gpu's flags
 
 
 class Shape(C.Structure):
@@ -207,7 +208,7 @@ ABI_SYMBOLS = (
     "svo_build_id", "svo_build_volume_gpu", "svo_tree_read_volume", "svo_volume_classify_pass",
     "svo_tree_patch_volume_gpu", "svo_tree_garbage", "svo_tree_patch_times", "svo_tree_compact_gpu", "svo_tree_compact_times",
     "svo_build_points_gpu", "svo_tree_get_blocks_gpu", "svo_tree_patch_points_gpu", "svo_tree_list_voxels_gpu",
-    "svo_tree_diff_gpu", "svo_tree_patch_shapes_gpu",
+    "svo_tree_diff_gpu", "svo_tree_patch_shapes_gpu", "svo_tree_patch_tree_gpu",
 )
 
 
@@ -298,7 +299,8 @@ def lib():
                      ("svo_tree_patch_points_gpu", [vp, vp, vp, C.c_int64]),
                      ("svo_tree_list_voxels_gpu", [vp, C.POINTER(i32), i32, i32, i32, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
                      ("svo_tree_diff_gpu", [vp, vp, C.POINTER(i32), i32, i32, i32, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
-                     ("svo_tree_patch_shapes_gpu", [vp, C.POINTER(Shape), i32])):
+                     ("svo_tree_patch_shapes_gpu", [vp, C.POINTER(Shape), i32]),
+                     ("svo_tree_patch_tree_gpu", [vp, vp, C.POINTER(i32), i32, i32, i32, C.POINTER(i32), C.c_uint32])):
         if hasattr(L, name):
             getattr(L, name).argtypes = at
     L.svo_build_terrain.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
@@ -850,16 +852,42 @@ class Tree:
         _check(lib().svo_tree_patch_shapes_gpu(self._h, arr if shapes else None, len(shapes)), "svo_tree_patch_shapes_gpu")
         return self
 
+    def patch_tree(self, src, src_origin, dims, dst_origin, keep_empty=False):
+        """svo_tree_patch_tree_gpu: paste the box of `dims` = (nx, ny, nz) voxels at `src_origin` (x, y, z) of the
+        (uploaded) tree `src` into this (uploaded) tree at `dst_origin`, on the device; src_origin None is src's whole
+        extent (dims is then not read).  Every voxel of the destination box takes what src stores at the matching
+        position (empty included), or with keep_empty only where src stores something; ids are numbers in this tree's
+        palette, and an id this tree's view does not store becomes empty.  The offset between the boxes is arbitrary, the
+        trees may have different levels, and src may be this tree (overlapping boxes copy the old content).  Uniform
+        regions of src are never expanded: the cost follows the box's surface and src's records in it.  The host image,
+        the ceilings and garbage() are brought up to date, and the call is complete on return; src is only read."""
+        if not isinstance(src, Tree):
+            raise ValueError("src: a Tree")
+        for t, name in ((self, "dst"), (src, "src")):
+            if t.info().device < 0:
+                raise SvoError("svo_tree_patch_tree_gpu failed (-4): tree %s not uploaded (svo_upload)" % name)
+        if len(dst_origin) != 3:
+            raise ValueError("dst_origin: three integers")
+        do = (C.c_int32 * 3)(*[int(v) for v in dst_origin])
+        so, n = None, (0, 0, 0)
+        if src_origin is not None:
+            if len(src_origin) != 3 or len(dims) != 3:
+                raise ValueError("src_origin, dims: three integers each")
+            so, n = (C.c_int32 * 3)(*[int(v) for v in src_origin]), tuple(int(v) for v in dims)
+        _check(lib().svo_tree_patch_tree_gpu(self._h, src._h, so, n[0], n[1], n[2], do, PASTE_KEEP_EMPTY if keep_empty else PASTE_REPLACE),
+               "svo_tree_patch_tree_gpu")
+        return self
+
     def garbage(self):
         """svo_tree_garbage: (node records, material entries) superseded by update() / patch_volume() / patch_points() /
-        patch_shapes() since the last
+        patch_shapes() / patch_tree() since the last
         full build or compact(): when they outweigh the tree, compact() pays"""
         n, m = C.c_uint64(), C.c_uint64()
         _check(lib().svo_tree_garbage(self._h, C.byref(n), C.byref(m)), "svo_tree_garbage")
         return n.value, m.value
 
     def patch_times(self):
-        """svo_tree_patch_times: host-clock ms of the last patch_volume(), patch_points() or patch_shapes() — (device passes, commit + host
+        """svo_tree_patch_times: host-clock ms of the last patch_volume(), patch_points(), patch_shapes() or patch_tree() — (device passes, commit + host
         image, ceilings)"""
         ms = (C.c_double * 3)()
         _check(lib().svo_tree_patch_times(self._h, ms), "svo_tree_patch_times")

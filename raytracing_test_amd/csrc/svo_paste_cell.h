@@ -1,0 +1,152 @@
+// svo_paste_cell.h — the cell logic of svo_tree_patch_tree_gpu (svo_patch_tree.hip), shared by its kernels and the host
+// (svo_plan.cpp: the garbage walk): no HIP, so it also builds with g++ and runs on a CPU
+// (tests/sanitize/paste_tree_plan_sanitize.cpp).  A paste copies the box [lo, hi) of the destination's extent from a
+// source tree, read at the destination's position plus `shift` (src_origin - dst_origin, on no grid).  How an aligned
+// destination cell of cs^3 voxels stands to the source is answered from the source's records, without expanding a
+// uniform region, and both sides of the patch ask through these functions: the device pass decides from the answer what a
+// child slot becomes, the host walk counts from it what the pass supersedes, and the two must agree on every cell.
+// The arrays may be the host images or the copies in HBM; every node and material index is widened to 64 bits before it
+// addresses memory.
+#pragma once
+
+#include <stdint.h>
+
+#include "svo_common.h"
+
+namespace svo {
+
+// a tree's arrays as the cell logic reads them
+struct PasteTree {
+    const Node* nodes;
+    const uint16_t* mats;
+    int32_t levels;
+};
+
+// A paste as the patch holds it, after the host's checks.
+struct PasteRec {
+    int32_t lo[3], hi[3];     // the destination box (hi = one past the last voxel), inside the destination's extent
+    int32_t shift[3];         // a destination voxel q reads the source at q + shift: lo + shift .. hi + shift lies inside src
+    uint32_t keep_empty;      // SVO_PASTE_KEEP_EMPTY: a voxel at which src stores nothing leaves dst as it is
+    const uint32_t* in_view;  // bit id: dst's view stores palette id (an id it does not hold is stored empty); NULL: all
+};
+
+enum : uint32_t { PASTE_OUT = 0u, PASTE_IN = 1u, PASTE_CUT = 2u };
+constexpr uint32_t kPasteMixed = 0xFFFFFFFFu;  // src_cell: not uniform (an id is below 65536)
+
+// the id as dst stores it
+SVO_HD uint32_t paste_resolve(const PasteRec& R, uint32_t id) {
+    return (!R.in_view || ((R.in_view[id >> 5] >> (id & 31u)) & 1u)) ? id : 0u;
+}
+
+// svo_tree_get_block's descent: the id the tree stores at a voxel of its extent, 0 for none
+SVO_HD uint32_t tree_voxel(const PasteTree& T, uint32_t x, uint32_t y, uint32_t z) {
+    uint64_t ni = 0;
+    for (int d = 0; d < T.levels; d++) {
+        const Node n = T.nodes[ni];
+        const uint32_t kind = node_kind(n.info);
+        if (kind == K_SOLID) return node_material(n.info);
+        if (kind == K_BRICK) {
+            const uint32_t v = ((z & 3u) << 4) | ((y & 3u) << 2) | (x & 3u);
+            if (!((n.mask >> v) & 1ull)) return 0u;
+            return (n.info & K_UNIFORM) ? node_material(n.info)
+                                        : T.mats[(uint64_t)n.ref + (uint64_t)__builtin_popcountll(n.mask & ((1ull << v) - 1ull))];
+        }
+        const uint32_t sh = (uint32_t)(2 * (T.levels - 1 - d));
+        const uint32_t sl = (((z >> sh) & 3u) << 4) | (((y >> sh) & 3u) << 2) | ((x >> sh) & 3u);
+        if (!((n.mask >> sl) & 1ull)) return 0u;
+        ni = (uint64_t)n.ref + (uint64_t)__builtin_popcountll(n.mask & ((1ull << sl) - 1ull));
+    }
+    return 0u;
+}
+
+// The aligned cell of src at depth `depth` (4^(levels - depth) voxels wide, depth <= levels - 1) that holds the voxel
+// (x, y, z): the id it holds throughout (0: nothing), or kPasteMixed.  Down from the root: a K_SOLID record at or above
+// the cell gives its id, a clear slot bit at or above it gives 0, a record at the cell's own level — K_INTERIOR with any
+// mask, K_BRICK — gives kPasteMixed.  The loop runs depth + 1 times whatever it finds (a finished walk re-reads its
+// last record), so that on the device its trip count is the same in all lanes.
+SVO_HD uint32_t src_cell(const PasteTree& S, int depth, uint32_t x, uint32_t y, uint32_t z) {
+    uint64_t ni = 0;
+    uint32_t res = kPasteMixed;
+    bool done = false;
+    for (int d = 0; d <= depth; d++) {
+        const Node n = S.nodes[ni];
+        const uint32_t kind = node_kind(n.info);
+        const uint32_t sh = (uint32_t)(2 * (S.levels - 1 - d));
+        const uint32_t sl = (((z >> sh) & 3u) << 4) | (((y >> sh) & 3u) << 2) | ((x >> sh) & 3u);
+        const bool has = (n.mask >> sl) & 1ull;
+        const uint64_t child = (uint64_t)n.ref + (uint64_t)__builtin_popcountll(n.mask & ((1ull << sl) - 1ull));
+        if (!done) {
+            if (kind == K_SOLID) {
+                res = node_material(n.info);
+                done = true;
+            } else if (d == depth || kind == K_BRICK) {
+                done = true;  // mixed
+            } else if (!has) {
+                res = 0u;
+                done = true;
+            } else {
+                ni = child;
+            }
+        }
+    }
+    return res;
+}
+
+// The aligned destination cell [x, x + cs) x [y, y + cs) x [z, z + cs), cs = 4^k with k >= 1, against the paste:
+//   OUT     no voxel of the cell changes: the cell does not meet the box, or (KEEP_EMPTY) src stores nothing in its part
+//           of the box, wherever the cell lies against the box;
+//   IN      the cell lies wholly inside the box and ends up uniformly *id (already resolved against dst's view; 0: empty);
+//   CUT     everything else: descend.
+// The cell is clipped to the box and shifted into src; the shifted region is at most cs wide per axis, so it meets at
+// most 2 x 2 x 2 aligned src cells of width min(cs, src's extent), and it is uniform when all of them are, with one id.
+// Conservative on purpose, as cell_relation is for late shapes: a mixed src cell whose overlapping part happens to be
+// uniform is CUT and comes out right at a finer level or at the voxels; a full one-material brick that stayed a brick and
+// an interior record with mask 0 count as mixed.  The result is content, not canonical layout.  All eight src cells are
+// walked even where they coincide, so that on the device every lane makes the same number of dependent loads.
+SVO_HD uint32_t paste_relation(const PasteRec& R, const PasteTree& S, int32_t x, int32_t y, int32_t z, int32_t cs, int k, uint32_t* id) {
+    const int32_t c[3] = {x, y, z};
+    bool out = false, in = true;
+    uint32_t a0[3], a1[3];
+    for (int a = 0; a < 3; a++) {
+        out = out || c[a] + cs <= R.lo[a] || c[a] >= R.hi[a];
+        in = in && c[a] >= R.lo[a] && c[a] + cs <= R.hi[a];
+        const int32_t lo = c[a] > R.lo[a] ? c[a] : R.lo[a], hi = c[a] + cs < R.hi[a] ? c[a] + cs : R.hi[a];
+        a0[a] = (uint32_t)(lo + R.shift[a]);      // the first and the last src voxel of the clipped cell
+        a1[a] = (uint32_t)(hi - 1 + R.shift[a]);  // (not read when the cell is out)
+    }
+    *id = 0u;
+    if (out) return PASTE_OUT;
+    const int depth = k < S.levels ? S.levels - k : 0;
+    uint32_t first = 0u;
+    bool uni = true;
+    for (uint32_t i = 0; i < 8u; i++) {
+        const uint32_t u = src_cell(S, depth, (i & 1u) ? a1[0] : a0[0], (i & 2u) ? a1[1] : a0[1], (i & 4u) ? a1[2] : a0[2]);
+        first = i == 0u ? u : first;
+        uni = uni && u != kPasteMixed && u == first;
+    }
+    if (uni && first == 0u && R.keep_empty) return PASTE_OUT;
+    if (uni && in) {
+        *id = paste_resolve(R, first);
+        return PASTE_IN;
+    }
+    return PASTE_CUT;
+}
+
+// one destination voxel: true when the paste decides it — the box holds it and the mode lets src's id through —, *id then
+// what dst stores there
+SVO_HD bool paste_takes(const PasteRec& R, const PasteTree& S, int32_t x, int32_t y, int32_t z, uint32_t* id) {
+    *id = 0u;
+    if (x < R.lo[0] || x >= R.hi[0] || y < R.lo[1] || y >= R.hi[1] || z < R.lo[2] || z >= R.hi[2]) return false;
+    const uint32_t s = tree_voxel(S, (uint32_t)(x + R.shift[0]), (uint32_t)(y + R.shift[1]), (uint32_t)(z + R.shift[2]));
+    if (s == 0u && R.keep_empty) return false;
+    *id = paste_resolve(R, s);
+    return true;
+}
+
+// the composite voxel after the paste: the paste's where it decides, else dst's own
+SVO_HD uint32_t paste_voxel(const PasteRec& R, const PasteTree& S, const PasteTree& D, int32_t x, int32_t y, int32_t z) {
+    uint32_t id;
+    return paste_takes(R, S, x, y, z, &id) ? id : tree_voxel(D, (uint32_t)x, (uint32_t)y, (uint32_t)z);
+}
+
+}  // namespace svo

@@ -1,0 +1,130 @@
+// svo_patch_tree.hip — svo_tree_patch_tree_gpu: a box of one resident tree (src) is pasted into another (dst), on the
+// device, at an offset that is on no grid, without expanding src's uniform regions: the cost follows the box's surface
+// and the src records reached in it, never the volume.  The descent, its kernels and its level loop are
+// svo_patch_cells.h's, shared with svo_patch_shapes.hip; the question a cell asks is svo_paste_cell.h's paste_relation:
+// the aligned destination cell is clipped to the box, shifted into src, and compared with the at most 2 x 2 x 2 aligned src
+// cells it meets, each found by a walk from src's root (eight walks of at most 7 dependent loads per lane, the same trip
+// count in every lane).  A cut brick's composite voxels come from src inside the box (where the mode lets them through)
+// and from dst elsewhere.
+// Everything is read from the arrays as they were on entry and written to scratch first, so src == dst with overlapping
+// boxes copies the old content; src is only ever read.  The descent starts at the anchor the host finds on dst's image
+// (svo_plan.cpp patch_anchor over the destination box), whose record is the only one rewritten in place; a REPLACE paste
+// over the whole extent restarts the arrays (the volume patch's rule).  The superseded records are counted by a host walk
+// (svo_plan.cpp paste_superseded) that asks the same paste_relation about the same cells over the two host images.
+// Every node and material index is widened to 64 bits before it addresses memory.
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <new>
+#include <vector>
+
+#include "../../include/svo_rt.h"
+#include "svo_hip.h"
+#include "svo_internal.h"
+#include "svo_paste_cell.h"
+#include "svo_patch_cells.h"
+
+using namespace svo;
+
+namespace {
+
+// the patch as svo_patch_cells.h's kernels ask it
+struct DevPaste {
+    PasteRec rec;  // (in_view: the bits in HBM, or NULL)
+    PasteTree src;
+    const Node* nodes;  // dst (read only: the patch is written to scratch)
+    const uint16_t* mats;
+    int32_t levels;
+    uint64_t nbase;  // scratch record s >= 1 becomes node nbase + s - 1 of dst
+    __device__ uint32_t relation(int32_t x, int32_t y, int32_t z, int32_t cs, int k, uint32_t* id) const {
+        return paste_relation(rec, src, x, y, z, cs, k, id);
+    }
+    __device__ bool voxel(int32_t x, int32_t y, int32_t z, uint32_t* id) const { return paste_takes(rec, src, x, y, z, id); }
+};
+
+}  // namespace
+
+extern "C" int svo_tree_patch_tree_gpu(svo_tree* dst, const svo_tree* src, const int32_t src_origin[3], int32_t nx, int32_t ny, int32_t nz,
+                                       const int32_t dst_origin[3], uint32_t flags) {
+    const char* who = "svo_tree_patch_tree_gpu";
+    if (!dst || !src) SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_gpu: NULL tree");
+    if (!dst_origin) SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_gpu: NULL dst_origin");
+    PastePlan plan;
+    switch (paste_plan(dst->levels, src->levels, src_origin, nx, ny, nz, dst_origin, flags, &plan)) {
+        case PASTE_FLAGS: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_gpu: unknown flag bits");
+        case PASTE_DIM: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_gpu: the box's dimensions must be positive");
+        case PASTE_SRC_EXTENT: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_gpu: the source box must lie within src's extent (no wrap)");
+        case PASTE_DST_EXTENT: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_gpu: the destination box must lie within dst's extent (no wrap)");
+        default: break;
+    }
+    const int32_t L = dst->levels;
+    if (L < 2 || dst->nodes.empty()) SVO_FAIL(SVO_ERANGE, "svo_tree_patch_tree_gpu: trees of fewer than 2 levels are not patched");
+    if (src->levels < 1 || src->nodes.empty()) SVO_FAIL(SVO_ERANGE, "svo_tree_patch_tree_gpu: src holds no tree");
+    if (dst->palette.empty() || dst->palette.size() > 65535) SVO_FAIL(SVO_ERANGE, "svo_tree_patch_tree_gpu: the palette must hold 1..65535 entries");
+    if (src->palette.size() > dst->palette.size())
+        SVO_FAIL(SVO_ERANGE, "svo_tree_patch_tree_gpu: src's palette holds more entries than dst's (ids are numbers in dst's palette)");
+    if (dst->device < 0 || !dst->d_nodes) SVO_FAIL(SVO_ESTATE, "svo_tree_patch_tree_gpu: tree dst not uploaded (svo_upload)");
+    if (src->device < 0 || !src->d_nodes) SVO_FAIL(SVO_ESTATE, "svo_tree_patch_tree_gpu: tree src not uploaded (svo_upload)");
+    if (src->device != dst->device) SVO_FAIL(SVO_ESTATE, "svo_tree_patch_tree_gpu: the trees are on different devices");
+    if (tree_unsynced(dst)) SVO_FAIL(SVO_ESTATE, "svo_tree_patch_tree_gpu: dst has host edits not yet synced (svo_tree_sync)");
+    if (tree_unsynced(src)) SVO_FAIL(SVO_ESTATE, "svo_tree_patch_tree_gpu: src has host edits not yet synced (svo_tree_sync)");
+
+    // the view table, the anchor and the superseded records: host work on the two images, before the first HIP call
+    const bool whole = plan.whole;
+    std::vector<uint32_t> bits;
+    std::vector<std::array<int64_t, 4>> rects;
+    PatchAnchor anchor;
+    uint64_t gnodes = 0, gmats = 0;
+    bool all = true;
+    try {
+        all = paste_view_bits(dst->palette, dst->view, &bits);
+        rects.push_back({plan.rec.lo[0], plan.rec.lo[2], plan.rec.hi[0], plan.rec.hi[2]});
+        dst->ceil_dirty.reserve(dst->ceil_dirty.size() + 1);
+    } catch (const std::bad_alloc&) {
+        SVO_FAIL(SVO_ENOMEM, "svo_tree_patch_tree_gpu: out of host memory");
+    }
+    anchor = patch_anchor(dst->nodes.data(), L, plan.rec.lo, plan.rec.hi);
+    anchor.whole = whole;  // (a KEEP_EMPTY paste over the whole extent stays at the root and restarts nothing)
+
+    HIP_TRY(hipSetDevice(dst->device), SVO_EDEVICE);
+    // records and ceilings are rewritten in place below: every cast over the tree must be over first (svo_tree_sync's
+    // contract)
+    HIP_TRY(hipDeviceSynchronize(), SVO_EDEVICE);
+    const auto clock0 = std::chrono::steady_clock::now();
+
+    const uint64_t nbase = whole ? 1 : dst->synced_nodes, mbase = whole ? 0 : dst->synced_mats;
+    if (!whole) {
+        PasteRec hrec = plan.rec;
+        hrec.in_view = all ? nullptr : bits.data();
+        paste_superseded(dst->nodes.data(), L, anchor, hrec, PasteTree{src->nodes.data(), src->mats.data(), src->levels}, &gnodes, &gmats);
+    }
+
+    Pool pool;
+    int rc = SVO_OK;
+    DevPaste P{plan.rec,
+               PasteTree{reinterpret_cast<const Node*>(src->d_nodes), reinterpret_cast<const uint16_t*>(src->d_mats), src->levels},
+               reinterpret_cast<const Node*>(dst->d_nodes),
+               reinterpret_cast<const uint16_t*>(dst->d_mats),
+               L,
+               nbase};
+    if (!all) {
+        uint32_t* dbits;
+        rc = pool.alloc(&dbits, bits.size());
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(dbits, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice), SVO_EDEVICE);
+        P.rec.in_view = dbits;
+    }
+
+    std::vector<void*> tmp;
+    struct TmpFree {
+        std::vector<void*>& v;
+        ~TmpFree() {
+            for (void* x : v) (void)hipFree(x);
+        }
+    } tmp_free{tmp};
+    CellsTail tail;
+    rc = descend_cells(P, who, anchor, nullptr, mbase, pool, tmp, &tail);
+    if (rc) return rc;
+    const auto clock1 = std::chrono::steady_clock::now();
+    return commit_cells(dst, who, tail, anchor, nbase, mbase, gnodes, gmats, rects, clock0, clock1);
+}

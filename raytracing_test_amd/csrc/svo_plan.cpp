@@ -473,13 +473,15 @@ int shapes_plan(int32_t levels, int32_t view, const std::vector<Material>& palet
 }
 
 namespace {
-struct ShapesSuperseded {
+// The walk shapes_superseded and paste_superseded share: rel(co, cs, k) is the device pass's own question about the child
+// cell at co, cs = 4^k voxels wide, answered SHAPE_OUT / SHAPE_IN / SHAPE_CUT (PASTE_* are the same numbers)
+template <class Rel>
+struct CellSuperseded {
     const Node* nodes;
     int32_t levels;
-    const ShapeRec* shapes;
-    int32_t n;
+    Rel rel;
     uint64_t n_nodes = 0, n_mats = 0;
-    // node ni's record is replaced: what hangs below it.  all: the cell lies wholly inside the deciding shape
+    // node ni's record is replaced: what hangs below it.  all: the cell lies wholly inside what replaces it
     void walk(uint32_t ni, const int32_t o[3], int depth, bool all) {
         const Node& nd = nodes[ni];
         const uint32_t kind = node_kind(nd.info);
@@ -489,7 +491,8 @@ struct ShapesSuperseded {
             return;
         }
         n_nodes += (uint64_t)__builtin_popcountll(nd.mask);
-        const int32_t cs = 1 << (2 * (levels - 1 - depth));
+        const int k = levels - 1 - depth;
+        const int32_t cs = 1 << (2 * k);
         uint64_t m = nd.mask;
         uint32_t ci = nd.ref;
         while (m) {
@@ -497,18 +500,72 @@ struct ShapesSuperseded {
             m &= m - 1;
             const uint32_t c = ci++;
             const int32_t co[3] = {o[0] + (int32_t)(sl & 3u) * cs, o[1] + (int32_t)((sl >> 2) & 3u) * cs, o[2] + (int32_t)(sl >> 4) * cs};
-            uint32_t id;
-            const uint32_t rel = all ? (uint32_t)SHAPE_IN : cell_relation(shapes, n, co[0], co[1], co[2], cs, &id);
-            if (rel == SHAPE_IN) walk(c, co, depth + 1, true);
-            else if (rel == SHAPE_CUT) walk(c, co, depth + 1, false);  // (no shape touches it: the copied record keeps its subtree)
+            const uint32_t r = all ? (uint32_t)SHAPE_IN : rel(co, cs, k);
+            if (r == SHAPE_IN) walk(c, co, depth + 1, true);
+            else if (r == SHAPE_CUT) walk(c, co, depth + 1, false);  // (untouched: the copied record keeps its subtree)
         }
     }
 };
+static_assert((uint32_t)PASTE_OUT == (uint32_t)SHAPE_OUT && (uint32_t)PASTE_IN == (uint32_t)SHAPE_IN &&
+                  (uint32_t)PASTE_CUT == (uint32_t)SHAPE_CUT,
+              "one walk serves both cell logics");
 }  // namespace
 
 void shapes_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const ShapeRec* shapes, int32_t n, uint64_t* n_nodes,
                        uint64_t* n_mats) {
-    ShapesSuperseded s{nodes, levels, shapes, n};
+    auto rel = [=](const int32_t co[3], int32_t cs, int) {
+        uint32_t id;
+        return cell_relation(shapes, n, co[0], co[1], co[2], cs, &id);
+    };
+    CellSuperseded<decltype(rel)> s{nodes, levels, rel};
+    s.walk(a.node, a.o, a.depth, false);
+    *n_nodes = s.n_nodes;
+    *n_mats = s.n_mats;
+}
+
+int paste_plan(int32_t dst_levels, int32_t src_levels, const int32_t* src_origin, int32_t nx, int32_t ny, int32_t nz, const int32_t dst_origin[3],
+               uint32_t flags, PastePlan* plan) {
+    if (flags & ~(uint32_t)SVO_PASTE_KEEP_EMPTY) return PASTE_FLAGS;
+    ListBox sb;
+    switch (list_box(src_levels, src_origin, nx, ny, nz, &sb)) {
+        case LIST_BOX_DIM: return PASTE_DIM;
+        case LIST_BOX_EXTENT: return PASTE_SRC_EXTENT;
+        default: break;
+    }
+    const int64_t E = (int64_t)1 << (2 * dst_levels);
+    PasteRec& r = plan->rec;
+    plan->whole = !(flags & SVO_PASTE_KEEP_EMPTY);
+    for (int a = 0; a < 3; a++) {
+        const int64_t dim = (int64_t)sb.hi[a] - sb.lo[a];
+        if (dst_origin[a] < 0 || (int64_t)dst_origin[a] + dim > E) return PASTE_DST_EXTENT;
+        r.lo[a] = dst_origin[a];
+        r.hi[a] = (int32_t)(dst_origin[a] + dim);
+        r.shift[a] = sb.lo[a] - dst_origin[a];
+        plan->whole = plan->whole && r.lo[a] == 0 && r.hi[a] == E;
+    }
+    r.keep_empty = flags & SVO_PASTE_KEEP_EMPTY;
+    r.in_view = nullptr;
+    return PASTE_OK;
+}
+
+bool paste_view_bits(const std::vector<Material>& palette, int32_t view, std::vector<uint32_t>* bits) {
+    bits->assign((palette.size() + 31) / 32, 0u);
+    bool all = true;
+    for (size_t i = 0; i < palette.size(); i++) {
+        const bool in = i == 0 || material_in_view(palette[i], view);
+        if (in) (*bits)[i >> 5] |= 1u << (i & 31u);
+        all = all && in;
+    }
+    return all;
+}
+
+void paste_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const PasteRec& rec, const PasteTree& src, uint64_t* n_nodes,
+                      uint64_t* n_mats) {
+    auto rel = [&](const int32_t co[3], int32_t cs, int k) {
+        uint32_t id;
+        return paste_relation(rec, src, co[0], co[1], co[2], cs, k, &id);
+    };
+    CellSuperseded<decltype(rel)> s{nodes, levels, rel};
     s.walk(a.node, a.o, a.depth, false);
     *n_nodes = s.n_nodes;
     *n_mats = s.n_mats;

@@ -6,6 +6,7 @@
 
 #include "svo_internal.h"
 #include "svo_list_unrank.h"
+#include "svo_paste_cell.h"
 #include "svo_shape_cell.h"
 
 namespace svo {
@@ -122,6 +123,32 @@ int shapes_plan(int32_t levels, int32_t view, const std::vector<Material>& palet
 // CUT, every subtree whose cell it calls IN, the material run of every brick whose cell is IN or CUT
 void shapes_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const ShapeRec* shapes, int32_t n, uint64_t* n_nodes,
                        uint64_t* n_mats);
+
+// svo_tree_patch_tree_gpu (svo_patch_tree.hip) pastes a box of one resident tree into another.  The host's part of it: the
+// flags and the two boxes checked (src_origin == NULL: src's whole extent, the dimensions then ignored; otherwise the list
+// box's rule for src, and the same box moved to dst_origin inside dst's extent, the sums taken in 64 bits), the paste as
+// the cells are asked against it (svo_paste_cell.h; in_view is left NULL for the caller to set), and whether it restarts
+// the arrays: a REPLACE paste whose destination box is the whole extent.
+enum : int {
+    PASTE_OK = 0,
+    PASTE_FLAGS = 1,       // an unknown flag bit
+    PASTE_DIM = 2,         // a non-positive dimension
+    PASTE_SRC_EXTENT = 3,  // the source box leaves src's extent
+    PASTE_DST_EXTENT = 4,  // the destination box leaves dst's extent
+};
+struct PastePlan {
+    PasteRec rec;
+    bool whole;
+};
+int paste_plan(int32_t dst_levels, int32_t src_levels, const int32_t* src_origin, int32_t nx, int32_t ny, int32_t nz, const int32_t dst_origin[3],
+               uint32_t flags, PastePlan* plan);
+// the in-view bit table of a palette under `view` (bit id: the view stores the id; bit 0 is set: id 0 stays 0); returns
+// true when every id is in view
+bool paste_view_bits(const std::vector<Material>& palette, int32_t view, std::vector<uint32_t>* bits);
+// shapes_superseded's walk over dst's host image with paste_relation asked over src's host image: what the paste
+// supersedes below the anchor, by the device pass's own rule
+void paste_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const PasteRec& rec, const PasteTree& src, uint64_t* n_nodes,
+                      uint64_t* n_mats);
 
 // svo_tree_list_voxels_gpu (svo_list_voxels.hip) lists the voxels inside a box of the extent 4^levels: origin == NULL is the
 // whole extent (the dimensions are then ignored), otherwise origin >= 0, origin + n <= extent and positive dimensions, with

@@ -33,7 +33,7 @@ extern "C" {
                              svo_tree_patch_times, svo_tree_compact_gpu, svo_tree_compact_times,
                              svo_build_points_gpu, svo_tree_get_blocks_gpu,
                              svo_tree_patch_points_gpu, svo_tree_list_voxels_gpu, svo_tree_diff_gpu,
-                             svo_tree_patch_shapes_gpu, svo_tree_patch_tree_gpu */
+                             svo_tree_patch_shapes_gpu, svo_tree_patch_tree_gpu, svo_tree_patch_tree_oriented_gpu */
 
 enum {
     SVO_OK = 0,
@@ -435,14 +435,55 @@ int svo_tree_patch_shapes_gpu(svo_tree* t, const svo_shape* shapes /* HOST */, i
    (svo_tree_sync).  SVO_ENOMEM: no scratch.
    The device is synchronised on entry (records and ceilings are rewritten in place: call it between frames); it runs on
    the null stream and the call is complete on return.  svo_tree_patch_times reports it.
-   Not done here: palette merging or id remapping, rotation or mirroring, lists of placements in one call. */
+   Rotation, mirroring and id remapping are svo_tree_patch_tree_oriented_gpu's, below.  Not done here or there: lists of
+   placements in one call. */
 #define SVO_PASTE_REPLACE 0     /* the box of dst becomes the box of src, empties included */
 #define SVO_PASTE_KEEP_EMPTY 1  /* voxels at which src stores nothing leave dst as it is (a prefab's air is transparent) */
 int svo_tree_patch_tree_gpu(svo_tree* dst, const svo_tree* src,
                             const int32_t src_origin[3], int32_t nx, int32_t ny, int32_t nz,
                             const int32_t dst_origin[3], uint32_t flags);
+/* The same paste turned, mirrored and with its ids remapped: a prefab built as its own small tree, with its own palette,
+   stamped in any of the 48 axis-aligned orientations.  svo_tree_patch_tree_gpu is the case axis = {0, 1, 2},
+   flip = {0, 0, 0}, id_map = NULL of this call, and keeps its own entry point.
+   Content.  The destination box is dst_origin + [0, dn) with dn[a] = n[axis[a]].  A voxel q of it has d = q - dst_origin
+   and reads src at s, where s[axis[a]] = src_origin[axis[a]] + (flip[a] ? n[axis[a]] - 1 - d[a] : d[a]): dst's axis a runs
+   along src's axis axis[a], against it where flip[a] is 1.  All 48 signed permutations are valid; the 24 of determinant
+   +1 are the rotations, the others mirrorings.  The id goes through four steps in this order: (1) src's id in src's own
+   view (a voxel src does not store reads 0); (2) id_map[id] when a map is given; (3) the mode, decided on the mapped id:
+   under SVO_PASTE_KEEP_EMPTY a material mapped to 0 is transparent, under SVO_PASTE_REPLACE it erases; (4) dst's view: an
+   id it does not hold is stored empty.  id_map is a HOST array with one entry per entry of src's palette (svo_tree_get_info's
+   n_materials of src), each an id of dst's palette; id_map[0] must be 0.  A map lifts the plain paste's rule that src's
+   palette be no larger than dst's: the map is the check.  There is still no palette growth: the ids mapped to must exist
+   in dst's palette.
+   Everything else is svo_tree_patch_tree_gpu's contract: src_origin and n as there, except that the whole of src is given
+   by its extent (there is no NULL origin in the struct); src == dst with overlapping boxes reads the content as it was
+   on entry, so a region can be rotated in place; a REPLACE paste whose destination box is the whole extent restarts the
+   arrays; one anchor record is rewritten in place; the host image, the ceilings over the destination box's footprint, the
+   top row and svo_tree_garbage's counts are brought up to date; svo_tree_patch_times reports the call; it synchronises on
+   entry and is complete on return.  The cost is the plain paste's: an orientation maps an aligned cell of cs voxels per
+   axis to a box of cs voxels per axis in src, which still meets at most 2 x 2 x 2 aligned src cells, so the work follows
+   the box's surface, never its volume.  The map is applied to what the walks return before cells are compared, so two src
+   cells of different ids that map to one id are one uniform region, and a region mapped to 0 is skipped under KEEP_EMPTY.
+   Scratch in HBM, freed on return: the plain paste's, and 2 B per entry of src's palette for the map.
+   All errors but the plain paste's last two are found on the host before the first HIP call: arguments first, then state.
+   After any error both trees are unchanged on host and device.
+   SVO_EINVAL: NULL dst, src or p; unknown flag bits; axis not a permutation of 0, 1, 2; a flip entry other than 0 or 1; a
+   non-positive dimension; either box leaving its extent (64-bit sums, no wrap); id_map[0] != 0.
+   SVO_ERANGE: a dst of one level; with a map, an entry >= dst's palette size (the message names the first such index);
+   without one, src's palette larger than dst's.  SVO_ESTATE, SVO_ENOMEM: as the plain paste.
+   Not done here: lists of placements in one call, palette growth. */
+typedef struct {
+    int32_t src_origin[3];   /* first voxel of the box in src */
+    int32_t n[3];            /* its dimensions along src's x, y, z; positive */
+    int32_t dst_origin[3];   /* first voxel of the destination box in dst */
+    uint32_t flags;          /* SVO_PASTE_REPLACE / SVO_PASTE_KEEP_EMPTY, no other bit */
+    uint8_t axis[3];         /* dst axis a runs along src axis axis[a]: a permutation of 0, 1, 2 */
+    uint8_t flip[3];         /* 0 or 1; 1: dst axis a runs against src axis axis[a] */
+    const uint16_t* id_map;  /* HOST array, one entry per entry of src's palette, or NULL (ids unchanged) */
+} svo_paste;
+int svo_tree_patch_tree_oriented_gpu(svo_tree* dst, const svo_tree* src, const svo_paste* p);
 /* node records and material entries superseded by edits (svo_tree_update, svo_tree_patch_volume_gpu,
-   svo_tree_patch_points_gpu, svo_tree_patch_shapes_gpu, svo_tree_patch_tree_gpu) since the last full build: still in the arrays, no longer reachable (either may be NULL) */
+   svo_tree_patch_points_gpu, svo_tree_patch_shapes_gpu, svo_tree_patch_tree_gpu, svo_tree_patch_tree_oriented_gpu) since the last full build: still in the arrays, no longer reachable (either may be NULL) */
 int svo_tree_garbage(const svo_tree* t, uint64_t* nodes, uint64_t* mats);
 /* diagnostics (tools/volume_patch_timing.py, tools/points_patch_timing.py): host-clock milliseconds of the tree's last
    svo_tree_patch_volume_gpu, svo_tree_patch_points_gpu, svo_tree_patch_shapes_gpu or svo_tree_patch_tree_gpu, whichever ran last, after its entry

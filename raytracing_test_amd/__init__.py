@@ -140,7 +140,15 @@ class PointsDesc(C.Structure):
 
 
 SHAPE_BOX, SHAPE_BALL = 0, 1
-PASTE_REPLACE, PASTE_KEEP_EMPTY = 0, 1   # svo_tree_patch_tree_gpu's flags
+PASTE_REPLACE, PASTE_KEEP_EMPTY = 0, 1   # svo_tree_patch_tree_gpu's and svo_paste's flags
+
+
+class Paste(C.Structure):
+    """svo_paste: svo_tree_patch_tree_oriented_gpu's placement — the source box, the destination's first voxel, the mode,
+    the orientation (dst axis a runs along src axis axis[a], against it where flip[a] is 1) and the host id map"""
+
+    _fields_ = [("src_origin", C.c_int32 * 3), ("n", C.c_int32 * 3), ("dst_origin", C.c_int32 * 3), ("flags", C.c_uint32),
+                ("axis", C.c_uint8 * 3), ("flip", C.c_uint8 * 3), ("id_map", C.POINTER(C.c_uint16))]
 
 
 class Shape(C.Structure):
@@ -208,7 +216,7 @@ ABI_SYMBOLS = (
     "svo_build_id", "svo_build_volume_gpu", "svo_tree_read_volume", "svo_volume_classify_pass",
     "svo_tree_patch_volume_gpu", "svo_tree_garbage", "svo_tree_patch_times", "svo_tree_compact_gpu", "svo_tree_compact_times",
     "svo_build_points_gpu", "svo_tree_get_blocks_gpu", "svo_tree_patch_points_gpu", "svo_tree_list_voxels_gpu",
-    "svo_tree_diff_gpu", "svo_tree_patch_shapes_gpu", "svo_tree_patch_tree_gpu",
+    "svo_tree_diff_gpu", "svo_tree_patch_shapes_gpu", "svo_tree_patch_tree_gpu", "svo_tree_patch_tree_oriented_gpu",
 )
 
 
@@ -300,7 +308,8 @@ def lib():
                      ("svo_tree_list_voxels_gpu", [vp, C.POINTER(i32), i32, i32, i32, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
                      ("svo_tree_diff_gpu", [vp, vp, C.POINTER(i32), i32, i32, i32, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
                      ("svo_tree_patch_shapes_gpu", [vp, C.POINTER(Shape), i32]),
-                     ("svo_tree_patch_tree_gpu", [vp, vp, C.POINTER(i32), i32, i32, i32, C.POINTER(i32), C.c_uint32])):
+                     ("svo_tree_patch_tree_gpu", [vp, vp, C.POINTER(i32), i32, i32, i32, C.POINTER(i32), C.c_uint32]),
+                     ("svo_tree_patch_tree_oriented_gpu", [vp, vp, C.POINTER(Paste)])):
         if hasattr(L, name):
             getattr(L, name).argtypes = at
     L.svo_build_terrain.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
@@ -876,6 +885,52 @@ class Tree:
             so, n = (C.c_int32 * 3)(*[int(v) for v in src_origin]), tuple(int(v) for v in dims)
         _check(lib().svo_tree_patch_tree_gpu(self._h, src._h, so, n[0], n[1], n[2], do, PASTE_KEEP_EMPTY if keep_empty else PASTE_REPLACE),
                "svo_tree_patch_tree_gpu")
+        return self
+
+    def patch_tree_oriented(self, src, src_origin, dims, dst_origin, axis=(0, 1, 2), flip=(0, 0, 0), id_map=None, keep_empty=False):
+        """svo_tree_patch_tree_oriented_gpu: patch_tree() turned, mirrored and with its ids remapped.  The box of `dims` =
+        (nx, ny, nz) voxels at `src_origin` of the (uploaded) tree `src` (src_origin None: the whole of src) goes to
+        `dst_origin` of this (uploaded) tree with this tree's axis a running along src's axis axis[a], against it where
+        flip[a] is 1: the destination box has dims[axis[a]] voxels along a, and its voxel dst_origin + d reads src at s with
+        s[axis[a]] = src_origin[axis[a]] + (dims[axis[a]] - 1 - d[a] if flip[a] else d[a]).  Any of the 48 signed axis
+        permutations is valid.  id_map: None, or a sequence or array with one entry per entry of src's palette, each an id
+        of this tree's palette and id_map[0] == 0; src's id goes through it first, then keep_empty decides on the mapped id
+        (a material mapped to 0 is transparent with keep_empty, erases without), then an id this tree's view does not store
+        becomes empty.  With a map src's palette may be larger than this tree's.  Cost, self-paste and what is brought up
+        to date are patch_tree()'s."""
+        if not isinstance(src, Tree):
+            raise ValueError("src: a Tree")
+        for t, name in ((self, "dst"), (src, "src")):
+            if t.info().device < 0:
+                raise SvoError("svo_tree_patch_tree_oriented_gpu failed (-4): tree %s not uploaded (svo_upload)" % name)
+        if len(dst_origin) != 3 or len(axis) != 3 or len(flip) != 3:
+            raise ValueError("dst_origin, axis, flip: three integers each")
+        p = Paste()
+        if src_origin is None:
+            e = 1 << (2 * src.info().levels)
+            src_origin, dims = (0, 0, 0), (e, e, e)
+        if len(src_origin) != 3 or len(dims) != 3:
+            raise ValueError("src_origin, dims: three integers each")
+        p.src_origin[:] = [int(v) for v in src_origin]
+        p.n[:] = [int(v) for v in dims]
+        p.dst_origin[:] = [int(v) for v in dst_origin]
+        p.flags = PASTE_KEEP_EMPTY if keep_empty else PASTE_REPLACE
+        for name, vals in (("axis", axis), ("flip", flip)):
+            vals = [int(v) for v in vals]
+            if any(v < 0 or v > 255 for v in vals):
+                raise ValueError("%s: entries out of range" % name)
+            getattr(p, name)[:] = vals
+        table = None
+        if id_map is not None:
+            vals = [int(v) for v in id_map]
+            if len(vals) != src.info().n_materials:
+                raise ValueError("id_map: one entry per entry of src's palette (%d)" % src.info().n_materials)
+            if any(v < 0 or v > 65535 for v in vals):
+                raise ValueError("id_map: ids are 0..65535")
+            table = (C.c_uint16 * max(1, len(vals)))(*vals)
+            p.id_map = C.cast(table, C.POINTER(C.c_uint16))
+        _check(lib().svo_tree_patch_tree_oriented_gpu(self._h, src._h, C.byref(p)), "svo_tree_patch_tree_oriented_gpu")
+        del table
         return self
 
     def garbage(self):

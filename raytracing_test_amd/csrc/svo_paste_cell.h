@@ -1,10 +1,13 @@
-// svo_paste_cell.h — the cell logic of svo_tree_patch_tree_gpu (svo_patch_tree.hip), shared by its kernels and the host
-// (svo_plan.cpp: the garbage walk): no HIP, so it also builds with g++ and runs on a CPU
-// (tests/sanitize/paste_tree_plan_sanitize.cpp).  A paste copies the box [lo, hi) of the destination's extent from a
-// source tree, read at the destination's position plus `shift` (src_origin - dst_origin, on no grid).  How an aligned
+// svo_paste_cell.h — the cell logic of svo_tree_patch_tree_gpu and svo_tree_patch_tree_oriented_gpu (svo_patch_tree.hip),
+// shared by their kernels and the host (svo_plan.cpp: the garbage walk): no HIP, so it also builds with g++ and runs on a
+// CPU (tests/sanitize/paste_tree_plan_sanitize.cpp, paste_oriented_plan_sanitize.cpp).  A paste copies the box [lo, hi) of
+// the destination's extent from a source tree, read at the destination's position plus `shift` (src_origin - dst_origin,
+// on no grid) or, oriented, through a per-axis affine map (PasteTurn), its ids through a table.  How an aligned
 // destination cell of cs^3 voxels stands to the source is answered from the source's records, without expanding a
 // uniform region, and both sides of the patch ask through these functions: the device pass decides from the answer what a
 // child slot becomes, the host walk counts from it what the pass supersedes, and the two must agree on every cell.
+// The functions are written once, over the record type: PasteRec is the identity orientation and the identity map at
+// compile time (the plain paste's kernels carry neither), PasteTurn the general case.
 // The arrays may be the host images or the copies in HBM; every node and material index is widened to 64 bits before it
 // addresses memory.
 #pragma once
@@ -30,8 +33,41 @@ struct PasteRec {
     const uint32_t* in_view;  // bit id: dst's view stores palette id (an id it does not hold is stored empty); NULL: all
 };
 
+// An oriented paste: a signed permutation of the axes and a table for the ids.  The destination voxel q reads the source
+// at s with s[axis[a]] = sign[a] * q[a] + shift[a]: PasteRec's shift is the map's offset here (for the identity the two
+// readings agree).  An aligned box of cs voxels per axis maps to a box of cs voxels per axis, so what paste_relation says
+// about the 2 x 2 x 2 aligned src cells holds as it stands.
+struct PasteTurn : PasteRec {
+    uint8_t axis[3];         // a permutation of 0, 1, 2
+    int8_t sign[3];          // +1, or -1 where dst's axis runs against src's
+    const uint16_t* id_map;  // one entry per entry of src's palette, [0] == 0 (host image or HBM, as the trees); NULL: none
+};
+
 enum : uint32_t { PASTE_OUT = 0u, PASTE_IN = 1u, PASTE_CUT = 2u };
 constexpr uint32_t kPasteMixed = 0xFFFFFFFFu;  // src_cell: not uniform (an id is below 65536)
+
+// where the destination voxel q reads the source
+SVO_HD void paste_source(const PasteRec& R, const int32_t q[3], uint32_t s[3]) {
+    for (int a = 0; a < 3; a++) s[a] = (uint32_t)(q[a] + R.shift[a]);
+}
+SVO_HD void paste_source(const PasteTurn& R, const int32_t q[3], uint32_t s[3]) {
+    for (int a = 0; a < 3; a++) {
+        const uint32_t v = (uint32_t)((int32_t)R.sign[a] * q[a] + R.shift[a]);
+        // (no indexing by axis[a]: the arrays stay in registers)
+        s[0] = R.axis[a] == 0 ? v : s[0];
+        s[1] = R.axis[a] == 1 ? v : s[1];
+        s[2] = R.axis[a] == 2 ? v : s[2];
+    }
+}
+
+// what src_cell or tree_voxel returned, through the id map: applied before the uniformity comparison and the mode.  The
+// table is read whatever the id is (kPasteMixed reads entry 0), so that every lane makes the same loads
+SVO_HD uint32_t paste_mapped(const PasteRec&, uint32_t id) { return id; }
+SVO_HD uint32_t paste_mapped(const PasteTurn& R, uint32_t id) {
+    if (!R.id_map) return id;
+    const uint32_t m = R.id_map[id == kPasteMixed ? 0u : id];
+    return id == kPasteMixed ? id : m;
+}
 
 // the id as dst stores it
 SVO_HD uint32_t paste_resolve(const PasteRec& R, uint32_t id) {
@@ -97,30 +133,36 @@ SVO_HD uint32_t src_cell(const PasteTree& S, int depth, uint32_t x, uint32_t y, 
 //           of the box, wherever the cell lies against the box;
 //   IN      the cell lies wholly inside the box and ends up uniformly *id (already resolved against dst's view; 0: empty);
 //   CUT     everything else: descend.
-// The cell is clipped to the box and shifted into src; the shifted region is at most cs wide per axis, so it meets at
-// most 2 x 2 x 2 aligned src cells of width min(cs, src's extent), and it is uniform when all of them are, with one id.
+// The cell is clipped to the box and its two ends are mapped into src (paste_source; under a flip the first end is the
+// higher one, and the eight corners take either end per src axis, so nothing is reordered); the mapped region is at most
+// cs wide per axis, so it meets at most 2 x 2 x 2 aligned src cells of width min(cs, src's extent), and it is uniform when
+// all of them are, with one mapped id (two src cells of different ids that map to one id count as uniform).
 // Conservative on purpose, as cell_relation is for late shapes: a mixed src cell whose overlapping part happens to be
 // uniform is CUT and comes out right at a finer level or at the voxels; a full one-material brick that stayed a brick and
 // an interior record with mask 0 count as mixed.  The result is content, not canonical layout.  All eight src cells are
 // walked even where they coincide, so that on the device every lane makes the same number of dependent loads.
-SVO_HD uint32_t paste_relation(const PasteRec& R, const PasteTree& S, int32_t x, int32_t y, int32_t z, int32_t cs, int k, uint32_t* id) {
+template <class Rec>
+SVO_HD uint32_t paste_relation(const Rec& R, const PasteTree& S, int32_t x, int32_t y, int32_t z, int32_t cs, int k, uint32_t* id) {
     const int32_t c[3] = {x, y, z};
     bool out = false, in = true;
-    uint32_t a0[3], a1[3];
+    int32_t q0[3], q1[3];
     for (int a = 0; a < 3; a++) {
         out = out || c[a] + cs <= R.lo[a] || c[a] >= R.hi[a];
         in = in && c[a] >= R.lo[a] && c[a] + cs <= R.hi[a];
         const int32_t lo = c[a] > R.lo[a] ? c[a] : R.lo[a], hi = c[a] + cs < R.hi[a] ? c[a] + cs : R.hi[a];
-        a0[a] = (uint32_t)(lo + R.shift[a]);      // the first and the last src voxel of the clipped cell
-        a1[a] = (uint32_t)(hi - 1 + R.shift[a]);  // (not read when the cell is out)
+        q0[a] = lo;  // the first and the last voxel of the clipped cell
+        q1[a] = hi - 1;
     }
+    uint32_t a0[3] = {0u, 0u, 0u}, a1[3] = {0u, 0u, 0u};  // the same two in src (not read when the cell is out)
+    paste_source(R, q0, a0);
+    paste_source(R, q1, a1);
     *id = 0u;
     if (out) return PASTE_OUT;
     const int depth = k < S.levels ? S.levels - k : 0;
     uint32_t first = 0u;
     bool uni = true;
     for (uint32_t i = 0; i < 8u; i++) {
-        const uint32_t u = src_cell(S, depth, (i & 1u) ? a1[0] : a0[0], (i & 2u) ? a1[1] : a0[1], (i & 4u) ? a1[2] : a0[2]);
+        const uint32_t u = paste_mapped(R, src_cell(S, depth, (i & 1u) ? a1[0] : a0[0], (i & 2u) ? a1[1] : a0[1], (i & 4u) ? a1[2] : a0[2]));
         first = i == 0u ? u : first;
         uni = uni && u != kPasteMixed && u == first;
     }
@@ -132,19 +174,24 @@ SVO_HD uint32_t paste_relation(const PasteRec& R, const PasteTree& S, int32_t x,
     return PASTE_CUT;
 }
 
-// one destination voxel: true when the paste decides it — the box holds it and the mode lets src's id through —, *id then
-// what dst stores there
-SVO_HD bool paste_takes(const PasteRec& R, const PasteTree& S, int32_t x, int32_t y, int32_t z, uint32_t* id) {
+// one destination voxel: true when the paste decides it — the box holds it and the mode lets src's mapped id through —,
+// *id then what dst stores there
+template <class Rec>
+SVO_HD bool paste_takes(const Rec& R, const PasteTree& S, int32_t x, int32_t y, int32_t z, uint32_t* id) {
     *id = 0u;
     if (x < R.lo[0] || x >= R.hi[0] || y < R.lo[1] || y >= R.hi[1] || z < R.lo[2] || z >= R.hi[2]) return false;
-    const uint32_t s = tree_voxel(S, (uint32_t)(x + R.shift[0]), (uint32_t)(y + R.shift[1]), (uint32_t)(z + R.shift[2]));
+    const int32_t q[3] = {x, y, z};
+    uint32_t p[3] = {0u, 0u, 0u};
+    paste_source(R, q, p);
+    const uint32_t s = paste_mapped(R, tree_voxel(S, p[0], p[1], p[2]));
     if (s == 0u && R.keep_empty) return false;
     *id = paste_resolve(R, s);
     return true;
 }
 
 // the composite voxel after the paste: the paste's where it decides, else dst's own
-SVO_HD uint32_t paste_voxel(const PasteRec& R, const PasteTree& S, const PasteTree& D, int32_t x, int32_t y, int32_t z) {
+template <class Rec>
+SVO_HD uint32_t paste_voxel(const Rec& R, const PasteTree& S, const PasteTree& D, int32_t x, int32_t y, int32_t z) {
     uint32_t id;
     return paste_takes(R, S, x, y, z, &id) ? id : tree_voxel(D, (uint32_t)x, (uint32_t)y, (uint32_t)z);
 }

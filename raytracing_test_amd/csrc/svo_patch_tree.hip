@@ -1,11 +1,15 @@
-// svo_patch_tree.hip — svo_tree_patch_tree_gpu: a box of one resident tree (src) is pasted into another (dst), on the
-// device, at an offset that is on no grid, without expanding src's uniform regions: the cost follows the box's surface
-// and the src records reached in it, never the volume.  The descent, its kernels and its level loop are
-// svo_patch_cells.h's, shared with svo_patch_shapes.hip; the question a cell asks is svo_paste_cell.h's paste_relation:
-// the aligned destination cell is clipped to the box, shifted into src, and compared with the at most 2 x 2 x 2 aligned src
-// cells it meets, each found by a walk from src's root (eight walks of at most 7 dependent loads per lane, the same trip
-// count in every lane).  A cut brick's composite voxels come from src inside the box (where the mode lets them through)
-// and from dst elsewhere.
+// svo_patch_tree.hip — svo_tree_patch_tree_gpu and svo_tree_patch_tree_oriented_gpu: a box of one resident tree (src) is
+// pasted into another (dst), on the device, at an offset that is on no grid — and, by the second call, turned or mirrored
+// by any of the 48 signed axis permutations, its ids through a table —, without expanding src's uniform regions: the cost
+// follows the box's surface and the src records reached in it, never the volume.  The descent, its kernels and its level
+// loop are svo_patch_cells.h's, shared with svo_patch_shapes.hip; the question a cell asks is svo_paste_cell.h's
+// paste_relation: the aligned destination cell is clipped to the box, its ends are mapped into src (a shift; oriented: a
+// per-axis affine map, under which an aligned cs^3 box is still a cs^3 box), and it is compared with the at most
+// 2 x 2 x 2 aligned src cells it meets, each found by a walk from src's root (eight walks of at most 7 dependent loads
+// per lane, the same trip count in every lane; with an id map one table load after each walk, in every lane too).  A cut
+// brick's composite voxels come from src inside the box (where the mode lets them through) and from dst elsewhere.
+// The two calls share everything but the record type the cell logic is instantiated over: PasteRec for the plain paste
+// (identity orientation and map at compile time: its kernels carry neither), PasteTurn for the oriented one.
 // Everything is read from the arrays as they were on entry and written to scratch first, so src == dst with overlapping
 // boxes copies the old content; src is only ever read.  The descent starts at the anchor the host finds on dst's image
 // (svo_plan.cpp patch_anchor over the destination box), whose record is the only one rewritten in place; a REPLACE paste
@@ -16,6 +20,7 @@
 
 #include <chrono>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "../../include/svo_rt.h"
@@ -28,9 +33,10 @@ using namespace svo;
 
 namespace {
 
-// the patch as svo_patch_cells.h's kernels ask it
-struct DevPaste {
-    PasteRec rec;  // (in_view: the bits in HBM, or NULL)
+// the patch as svo_patch_cells.h's kernels ask it, over the record type of the cell logic
+template <class Rec>
+struct DevPasteOf {
+    Rec rec;  // (in_view, id_map: the tables in HBM, or NULL)
     PasteTree src;
     const Node* nodes;  // dst (read only: the patch is written to scratch)
     const uint16_t* mats;
@@ -41,6 +47,107 @@ struct DevPaste {
     }
     __device__ bool voxel(int32_t x, int32_t y, int32_t z, uint32_t* id) const { return paste_takes(rec, src, x, y, z, id); }
 };
+struct DevPaste : DevPasteOf<PasteRec> {};      // svo_tree_patch_tree_gpu
+struct DevPasteTurn : DevPasteOf<PasteTurn> {};  // svo_tree_patch_tree_oriented_gpu
+
+// the id map (a host array of n entries) to the device, where the record has one
+int upload_id_map(Pool&, PasteRec&, size_t) { return SVO_OK; }
+int upload_id_map(Pool& pool, PasteTurn& rec, size_t n) {
+    if (!rec.id_map) return SVO_OK;
+    uint16_t* dmap;
+    const int rc = pool.alloc(&dmap, n);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(dmap, rec.id_map, n * sizeof(uint16_t), hipMemcpyHostToDevice), SVO_EDEVICE);
+    rec.id_map = dmap;
+    return SVO_OK;
+}
+
+// The checks on the trees, after the arguments' and before the first HIP call.  id_map: the oriented call's table (its
+// entries are then the range check), or NULL: ids are numbers in dst's palette
+int paste_check_trees(const svo_tree* dst, const svo_tree* src, const std::string& who, const uint16_t* id_map) {
+    if (dst->levels < 2 || dst->nodes.empty()) SVO_FAIL(SVO_ERANGE, who + ": trees of fewer than 2 levels are not patched");
+    if (src->levels < 1 || src->nodes.empty()) SVO_FAIL(SVO_ERANGE, who + ": src holds no tree");
+    if (dst->palette.empty() || dst->palette.size() > 65535) SVO_FAIL(SVO_ERANGE, who + ": the palette must hold 1..65535 entries");
+    if (id_map) {
+        for (size_t i = 0; i < src->palette.size(); i++)
+            if (id_map[i] >= dst->palette.size())
+                SVO_FAIL(SVO_ERANGE, who + ": id_map[" + std::to_string(i) + "] = " + std::to_string(id_map[i]) + " is not an id of dst's palette (" +
+                                         std::to_string(dst->palette.size()) + " entries)");
+    } else if (src->palette.size() > dst->palette.size()) {
+        SVO_FAIL(SVO_ERANGE, who + ": src's palette holds more entries than dst's (ids are numbers in dst's palette)");
+    }
+    if (dst->device < 0 || !dst->d_nodes) SVO_FAIL(SVO_ESTATE, who + ": tree dst not uploaded (svo_upload)");
+    if (src->device < 0 || !src->d_nodes) SVO_FAIL(SVO_ESTATE, who + ": tree src not uploaded (svo_upload)");
+    if (src->device != dst->device) SVO_FAIL(SVO_ESTATE, who + ": the trees are on different devices");
+    if (tree_unsynced(dst)) SVO_FAIL(SVO_ESTATE, who + ": dst has host edits not yet synced (svo_tree_sync)");
+    if (tree_unsynced(src)) SVO_FAIL(SVO_ESTATE, who + ": src has host edits not yet synced (svo_tree_sync)");
+    return SVO_OK;
+}
+
+// The paste itself, the same for both calls.  rec: the plan's record (in_view NULL; id_map the host array or NULL)
+template <class Dev, class Rec>
+int paste_run(svo_tree* dst, const svo_tree* src, const char* who, const Rec& rec, bool whole) {
+    const int32_t L = dst->levels;
+    // the view table, the anchor and the superseded records: host work on the two images, before the first HIP call
+    std::vector<uint32_t> bits;
+    std::vector<std::array<int64_t, 4>> rects;
+    PatchAnchor anchor;
+    uint64_t gnodes = 0, gmats = 0;
+    bool all = true;
+    try {
+        all = paste_view_bits(dst->palette, dst->view, &bits);
+        rects.push_back({rec.lo[0], rec.lo[2], rec.hi[0], rec.hi[2]});
+        dst->ceil_dirty.reserve(dst->ceil_dirty.size() + 1);
+    } catch (const std::bad_alloc&) {
+        SVO_FAIL(SVO_ENOMEM, std::string(who) + ": out of host memory");
+    }
+    anchor = patch_anchor(dst->nodes.data(), L, rec.lo, rec.hi);
+    anchor.whole = whole;  // (a KEEP_EMPTY paste over the whole extent stays at the root and restarts nothing)
+
+    HIP_TRY(hipSetDevice(dst->device), SVO_EDEVICE);
+    // records and ceilings are rewritten in place below: every cast over the tree must be over first (svo_tree_sync's
+    // contract)
+    HIP_TRY(hipDeviceSynchronize(), SVO_EDEVICE);
+    const auto clock0 = std::chrono::steady_clock::now();
+
+    const uint64_t nbase = whole ? 1 : dst->synced_nodes, mbase = whole ? 0 : dst->synced_mats;
+    if (!whole) {
+        Rec hrec = rec;
+        hrec.in_view = all ? nullptr : bits.data();
+        paste_superseded(dst->nodes.data(), L, anchor, hrec, PasteTree{src->nodes.data(), src->mats.data(), src->levels}, &gnodes, &gmats);
+    }
+
+    Pool pool;
+    int rc = SVO_OK;
+    Dev P{{rec,
+           PasteTree{reinterpret_cast<const Node*>(src->d_nodes), reinterpret_cast<const uint16_t*>(src->d_mats), src->levels},
+           reinterpret_cast<const Node*>(dst->d_nodes),
+           reinterpret_cast<const uint16_t*>(dst->d_mats),
+           L,
+           nbase}};
+    if (!all) {
+        uint32_t* dbits;
+        rc = pool.alloc(&dbits, bits.size());
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy(dbits, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice), SVO_EDEVICE);
+        P.rec.in_view = dbits;
+    }
+    rc = upload_id_map(pool, P.rec, src->palette.size());
+    if (rc) return rc;
+
+    std::vector<void*> tmp;
+    struct TmpFree {
+        std::vector<void*>& v;
+        ~TmpFree() {
+            for (void* x : v) (void)hipFree(x);
+        }
+    } tmp_free{tmp};
+    CellsTail tail;
+    rc = descend_cells(P, who, anchor, nullptr, mbase, pool, tmp, &tail);
+    if (rc) return rc;
+    const auto clock1 = std::chrono::steady_clock::now();
+    return commit_cells(dst, who, tail, anchor, nbase, mbase, gnodes, gmats, rects, clock0, clock1);
+}
 
 }  // namespace
 
@@ -57,74 +164,29 @@ extern "C" int svo_tree_patch_tree_gpu(svo_tree* dst, const svo_tree* src, const
         case PASTE_DST_EXTENT: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_gpu: the destination box must lie within dst's extent (no wrap)");
         default: break;
     }
-    const int32_t L = dst->levels;
-    if (L < 2 || dst->nodes.empty()) SVO_FAIL(SVO_ERANGE, "svo_tree_patch_tree_gpu: trees of fewer than 2 levels are not patched");
-    if (src->levels < 1 || src->nodes.empty()) SVO_FAIL(SVO_ERANGE, "svo_tree_patch_tree_gpu: src holds no tree");
-    if (dst->palette.empty() || dst->palette.size() > 65535) SVO_FAIL(SVO_ERANGE, "svo_tree_patch_tree_gpu: the palette must hold 1..65535 entries");
-    if (src->palette.size() > dst->palette.size())
-        SVO_FAIL(SVO_ERANGE, "svo_tree_patch_tree_gpu: src's palette holds more entries than dst's (ids are numbers in dst's palette)");
-    if (dst->device < 0 || !dst->d_nodes) SVO_FAIL(SVO_ESTATE, "svo_tree_patch_tree_gpu: tree dst not uploaded (svo_upload)");
-    if (src->device < 0 || !src->d_nodes) SVO_FAIL(SVO_ESTATE, "svo_tree_patch_tree_gpu: tree src not uploaded (svo_upload)");
-    if (src->device != dst->device) SVO_FAIL(SVO_ESTATE, "svo_tree_patch_tree_gpu: the trees are on different devices");
-    if (tree_unsynced(dst)) SVO_FAIL(SVO_ESTATE, "svo_tree_patch_tree_gpu: dst has host edits not yet synced (svo_tree_sync)");
-    if (tree_unsynced(src)) SVO_FAIL(SVO_ESTATE, "svo_tree_patch_tree_gpu: src has host edits not yet synced (svo_tree_sync)");
-
-    // the view table, the anchor and the superseded records: host work on the two images, before the first HIP call
-    const bool whole = plan.whole;
-    std::vector<uint32_t> bits;
-    std::vector<std::array<int64_t, 4>> rects;
-    PatchAnchor anchor;
-    uint64_t gnodes = 0, gmats = 0;
-    bool all = true;
-    try {
-        all = paste_view_bits(dst->palette, dst->view, &bits);
-        rects.push_back({plan.rec.lo[0], plan.rec.lo[2], plan.rec.hi[0], plan.rec.hi[2]});
-        dst->ceil_dirty.reserve(dst->ceil_dirty.size() + 1);
-    } catch (const std::bad_alloc&) {
-        SVO_FAIL(SVO_ENOMEM, "svo_tree_patch_tree_gpu: out of host memory");
-    }
-    anchor = patch_anchor(dst->nodes.data(), L, plan.rec.lo, plan.rec.hi);
-    anchor.whole = whole;  // (a KEEP_EMPTY paste over the whole extent stays at the root and restarts nothing)
-
-    HIP_TRY(hipSetDevice(dst->device), SVO_EDEVICE);
-    // records and ceilings are rewritten in place below: every cast over the tree must be over first (svo_tree_sync's
-    // contract)
-    HIP_TRY(hipDeviceSynchronize(), SVO_EDEVICE);
-    const auto clock0 = std::chrono::steady_clock::now();
-
-    const uint64_t nbase = whole ? 1 : dst->synced_nodes, mbase = whole ? 0 : dst->synced_mats;
-    if (!whole) {
-        PasteRec hrec = plan.rec;
-        hrec.in_view = all ? nullptr : bits.data();
-        paste_superseded(dst->nodes.data(), L, anchor, hrec, PasteTree{src->nodes.data(), src->mats.data(), src->levels}, &gnodes, &gmats);
-    }
-
-    Pool pool;
-    int rc = SVO_OK;
-    DevPaste P{plan.rec,
-               PasteTree{reinterpret_cast<const Node*>(src->d_nodes), reinterpret_cast<const uint16_t*>(src->d_mats), src->levels},
-               reinterpret_cast<const Node*>(dst->d_nodes),
-               reinterpret_cast<const uint16_t*>(dst->d_mats),
-               L,
-               nbase};
-    if (!all) {
-        uint32_t* dbits;
-        rc = pool.alloc(&dbits, bits.size());
-        if (rc) return rc;
-        HIP_TRY(hipMemcpy(dbits, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice), SVO_EDEVICE);
-        P.rec.in_view = dbits;
-    }
-
-    std::vector<void*> tmp;
-    struct TmpFree {
-        std::vector<void*>& v;
-        ~TmpFree() {
-            for (void* x : v) (void)hipFree(x);
-        }
-    } tmp_free{tmp};
-    CellsTail tail;
-    rc = descend_cells(P, who, anchor, nullptr, mbase, pool, tmp, &tail);
+    const int rc = paste_check_trees(dst, src, who, nullptr);
     if (rc) return rc;
-    const auto clock1 = std::chrono::steady_clock::now();
-    return commit_cells(dst, who, tail, anchor, nbase, mbase, gnodes, gmats, rects, clock0, clock1);
+    return paste_run<DevPaste, PasteRec>(dst, src, who, plan.rec, plan.whole);
+}
+
+extern "C" int svo_tree_patch_tree_oriented_gpu(svo_tree* dst, const svo_tree* src, const svo_paste* p) {
+    const char* who = "svo_tree_patch_tree_oriented_gpu";
+    if (!dst || !src) SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_oriented_gpu: NULL tree");
+    if (!p) SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_oriented_gpu: NULL svo_paste");
+    PastePlan plan;
+    switch (paste_plan(dst->levels, src->levels, p->src_origin, p->n[0], p->n[1], p->n[2], p->dst_origin, p->flags, &plan, p->axis, p->flip)) {
+        case PASTE_FLAGS: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_oriented_gpu: unknown flag bits");
+        case PASTE_AXIS: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_oriented_gpu: axis must be a permutation of 0, 1, 2");
+        case PASTE_FLIP: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_oriented_gpu: flip entries must be 0 or 1");
+        case PASTE_DIM: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_oriented_gpu: the box's dimensions must be positive");
+        case PASTE_SRC_EXTENT: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_oriented_gpu: the source box must lie within src's extent (no wrap)");
+        case PASTE_DST_EXTENT:
+            SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_oriented_gpu: the destination box (the dimensions permuted by axis) must lie within dst's extent (no wrap)");
+        default: break;
+    }
+    if (p->id_map && !src->palette.empty() && p->id_map[0] != 0) SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_oriented_gpu: id_map[0] must be 0");
+    const int rc = paste_check_trees(dst, src, who, p->id_map);
+    if (rc) return rc;
+    plan.rec.id_map = p->id_map;
+    return paste_run<DevPasteTurn, PasteTurn>(dst, src, who, plan.rec, plan.whole);
 }

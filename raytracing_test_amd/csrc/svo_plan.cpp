@@ -524,8 +524,20 @@ void shapes_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, 
 }
 
 int paste_plan(int32_t dst_levels, int32_t src_levels, const int32_t* src_origin, int32_t nx, int32_t ny, int32_t nz, const int32_t dst_origin[3],
-               uint32_t flags, PastePlan* plan) {
+               uint32_t flags, PastePlan* plan, const uint8_t* axis, const uint8_t* flip) {
     if (flags & ~(uint32_t)SVO_PASTE_KEEP_EMPTY) return PASTE_FLAGS;
+    PasteTurn& r = plan->rec;
+    uint32_t seen = 0u;
+    for (int a = 0; a < 3; a++) {
+        r.axis[a] = axis ? axis[a] : (uint8_t)a;
+        if (r.axis[a] > 2) return PASTE_AXIS;
+        seen |= 1u << r.axis[a];
+    }
+    if (seen != 7u) return PASTE_AXIS;
+    for (int a = 0; a < 3; a++) {
+        if (flip && flip[a] > 1) return PASTE_FLIP;
+        r.sign[a] = flip && flip[a] ? -1 : 1;
+    }
     ListBox sb;
     switch (list_box(src_levels, src_origin, nx, ny, nz, &sb)) {
         case LIST_BOX_DIM: return PASTE_DIM;
@@ -533,18 +545,19 @@ int paste_plan(int32_t dst_levels, int32_t src_levels, const int32_t* src_origin
         default: break;
     }
     const int64_t E = (int64_t)1 << (2 * dst_levels);
-    PasteRec& r = plan->rec;
     plan->whole = !(flags & SVO_PASTE_KEEP_EMPTY);
     for (int a = 0; a < 3; a++) {
-        const int64_t dim = (int64_t)sb.hi[a] - sb.lo[a];
+        const int j = r.axis[a];
+        const int64_t dim = (int64_t)sb.hi[j] - sb.lo[j];
         if (dst_origin[a] < 0 || (int64_t)dst_origin[a] + dim > E) return PASTE_DST_EXTENT;
         r.lo[a] = dst_origin[a];
         r.hi[a] = (int32_t)(dst_origin[a] + dim);
-        r.shift[a] = sb.lo[a] - dst_origin[a];
+        r.shift[a] = r.sign[a] > 0 ? sb.lo[j] - dst_origin[a] : sb.hi[j] - 1 + dst_origin[a];  // (both extents are at most 2^14)
         plan->whole = plan->whole && r.lo[a] == 0 && r.hi[a] == E;
     }
     r.keep_empty = flags & SVO_PASTE_KEEP_EMPTY;
     r.in_view = nullptr;
+    r.id_map = nullptr;
     return PASTE_OK;
 }
 
@@ -559,8 +572,10 @@ bool paste_view_bits(const std::vector<Material>& palette, int32_t view, std::ve
     return all;
 }
 
-void paste_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const PasteRec& rec, const PasteTree& src, uint64_t* n_nodes,
-                      uint64_t* n_mats) {
+namespace {
+template <class Rec>
+void paste_superseded_as(const Node* nodes, int32_t levels, const PatchAnchor& a, const Rec& rec, const PasteTree& src, uint64_t* n_nodes,
+                         uint64_t* n_mats) {
     auto rel = [&](const int32_t co[3], int32_t cs, int k) {
         uint32_t id;
         return paste_relation(rec, src, co[0], co[1], co[2], cs, k, &id);
@@ -569,6 +584,17 @@ void paste_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, c
     s.walk(a.node, a.o, a.depth, false);
     *n_nodes = s.n_nodes;
     *n_mats = s.n_mats;
+}
+}  // namespace
+
+void paste_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const PasteRec& rec, const PasteTree& src, uint64_t* n_nodes,
+                      uint64_t* n_mats) {
+    paste_superseded_as(nodes, levels, a, rec, src, n_nodes, n_mats);
+}
+
+void paste_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const PasteTurn& rec, const PasteTree& src, uint64_t* n_nodes,
+                      uint64_t* n_mats) {
+    paste_superseded_as(nodes, levels, a, rec, src, n_nodes, n_mats);
 }
 
 int list_box(int32_t levels, const int32_t* origin, int32_t nx, int32_t ny, int32_t nz, ListBox* B) {

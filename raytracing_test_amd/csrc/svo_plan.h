@@ -129,25 +129,34 @@ void shapes_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, 
 // box's rule for src, and the same box moved to dst_origin inside dst's extent, the sums taken in 64 bits), the paste as
 // the cells are asked against it (svo_paste_cell.h; in_view is left NULL for the caller to set), and whether it restarts
 // the arrays: a REPLACE paste whose destination box is the whole extent.
+// svo_tree_patch_tree_oriented_gpu adds the orientation (svo_paste's axis and flip; NULL: the identity): checked after the
+// flags and before the boxes, it gives the destination box its dimensions dn[a] = n[axis[a]] and the record its affine
+// map, s[axis[a]] = sign[a] * q[a] + shift[a] with shift[a] = src_origin[axis[a]] - dst_origin[a], or under a flip
+// src_origin[axis[a]] + n[axis[a]] - 1 + dst_origin[a].  rec.id_map is left NULL for the caller to set.  Sliced to its
+// PasteRec, the record of an identity plan is the plain paste's.
 enum : int {
     PASTE_OK = 0,
     PASTE_FLAGS = 1,       // an unknown flag bit
     PASTE_DIM = 2,         // a non-positive dimension
     PASTE_SRC_EXTENT = 3,  // the source box leaves src's extent
     PASTE_DST_EXTENT = 4,  // the destination box leaves dst's extent
+    PASTE_AXIS = 5,        // axis is not a permutation of 0, 1, 2
+    PASTE_FLIP = 6,        // a flip entry other than 0 or 1
 };
 struct PastePlan {
-    PasteRec rec;
+    PasteTurn rec;
     bool whole;
 };
 int paste_plan(int32_t dst_levels, int32_t src_levels, const int32_t* src_origin, int32_t nx, int32_t ny, int32_t nz, const int32_t dst_origin[3],
-               uint32_t flags, PastePlan* plan);
+               uint32_t flags, PastePlan* plan, const uint8_t* axis = nullptr, const uint8_t* flip = nullptr);
 // the in-view bit table of a palette under `view` (bit id: the view stores the id; bit 0 is set: id 0 stays 0); returns
 // true when every id is in view
 bool paste_view_bits(const std::vector<Material>& palette, int32_t view, std::vector<uint32_t>* bits);
 // shapes_superseded's walk over dst's host image with paste_relation asked over src's host image: what the paste
 // supersedes below the anchor, by the device pass's own rule
 void paste_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const PasteRec& rec, const PasteTree& src, uint64_t* n_nodes,
+                      uint64_t* n_mats);
+void paste_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const PasteTurn& rec, const PasteTree& src, uint64_t* n_nodes,
                       uint64_t* n_mats);
 
 // svo_tree_list_voxels_gpu (svo_list_voxels.hip) lists the voxels inside a box of the extent 4^levels: origin == NULL is the

@@ -33,7 +33,8 @@ extern "C" {
                              svo_tree_patch_times, svo_tree_compact_gpu, svo_tree_compact_times,
                              svo_build_points_gpu, svo_tree_get_blocks_gpu,
                              svo_tree_patch_points_gpu, svo_tree_list_voxels_gpu, svo_tree_diff_gpu,
-                             svo_tree_patch_shapes_gpu, svo_tree_patch_tree_gpu, svo_tree_patch_tree_oriented_gpu */
+                             svo_tree_patch_shapes_gpu, svo_tree_patch_tree_gpu, svo_tree_patch_tree_oriented_gpu,
+                             svo_tree_patch_tree_rule_gpu */
 
 enum {
     SVO_OK = 0,
@@ -482,11 +483,61 @@ typedef struct {
     const uint16_t* id_map;  /* HOST array, one entry per entry of src's palette, or NULL (ids unchanged) */
 } svo_paste;
 int svo_tree_patch_tree_oriented_gpu(svo_tree* dst, const svo_tree* src, const svo_paste* p);
+/* The oriented paste under a rule over both sides: the two calls above decide every voxel from src alone, this one also
+   asks what dst holds, so a prefab can fill only air (UNDER), recolour only what is solid (PAINT), carve (ERASE), or act as
+   a mask, a stencil or a symmetric difference.  p gives the geometry, the orientation and the id map exactly as for
+   svo_tree_patch_tree_oriented_gpu; p->flags must be 0, because the rule replaces it.
+   For each voxel q of the destination box: s is src's id read through the orientation and then id_map (steps (1) and (2)
+   above); d is the id dst stores at q on entry, IN DST'S OWN VIEW; R(s) is s resolved against dst's view (an id the view
+   does not hold is stored empty).  The rule says what q holds afterwards in the three cases that are not trivially empty:
+                                       SVO_RULE_KEEP   SVO_RULE_TAKE   SVO_RULE_CLEAR
+     A "src only"  s != 0, d == 0           0              R(s)         not allowed
+     B "both"      s != 0, d != 0           d              R(s)              0
+     C "dst only"  s == 0, d != 0           d           not allowed          0
+   and s == 0, d == 0 stays 0.  rule = SVO_RULE(A, B, C) = A | B << 2 | C << 4: 12 rules, the useful ones named below.
+   SVO_RULE_OVER has SVO_PASTE_KEEP_EMPTY's content and SVO_RULE_REPLACE has SVO_PASTE_REPLACE's.  Rule 0 keeps everything:
+   it returns SVO_OK after the argument and state checks, without device work.
+   Because d is read in dst's own view, a rule whose outcome depends on d, pasted into the solid-view tree and into the
+   full-view tree of one world, does NOT leave them the two views of one pasted world: a liquid voxel is d == 0 in the solid
+   view, so SVO_RULE_UNDER of a solid material over water stores the solid in the solid-view tree and keeps the water in the
+   full-view tree.
+   Every voxel outside the destination box is as before; with src == dst and overlapping boxes everything is read as it was
+   on entry; src is only read.  The call never restarts the arrays, whatever the rule and the box (svo_tree_compact_gpu
+   exists).  Everything else is the oriented paste's contract: one anchor record is rewritten in place; the host image, the
+   ceilings over the destination box's footprint, the top row and svo_tree_garbage's counts are brought up to date;
+   svo_tree_patch_times reports the call; it synchronises on entry and is complete on return.
+   Cost.  The descent is the paste's, with one more walk per cell: the destination cell itself is looked up in dst (uniform,
+   empty, or a record at its level), and the two answers are combined.  Uniform against uniform is decided at the cell.  A
+   cell is re-emitted one level down only where the box's surface cuts it, where a src record of its level overlaps it, or,
+   for rules whose outcome depends on d, where dst holds a record of its level under a non-empty src region; where the rule
+   keeps whatever dst holds the cell keeps its record and subtree.  The work follows surfaces and records, never the volume.
+   Scratch in HBM: the oriented paste's.
+   Errors are found on the host before the first HIP call, arguments first, then state; after any error both trees are
+   unchanged on host and device.
+   SVO_EINVAL: NULL dst, src or p; p->flags != 0; a rule with a bit above 5, with A not KEEP or TAKE, B == 3, or C not KEEP
+   or CLEAR; and the oriented paste's own cases (axis, flip, dimensions, either extent, id_map[0] != 0).
+   SVO_ERANGE, SVO_ESTATE, SVO_ENOMEM: as the oriented paste.
+   Not done here: lists of placements in one call, palette growth. */
+#define SVO_RULE_KEEP 0u  /* the voxel stays as dst has it (case A: empty) */
+#define SVO_RULE_TAKE 1u  /* the voxel takes src's mapped id, resolved against dst's view (cases A and B) */
+#define SVO_RULE_CLEAR 2u /* the voxel becomes empty (cases B and C) */
+#define SVO_RULE(a, b, c) ((uint32_t)(a) | (uint32_t)(b) << 2 | (uint32_t)(c) << 4)
+#define SVO_RULE_UNDER 1u    /* (TAKE, KEEP, KEEP): fill only air */
+#define SVO_RULE_PAINT 4u    /* (KEEP, TAKE, KEEP): recolour only what is solid */
+#define SVO_RULE_OVER 5u     /* (TAKE, TAKE, KEEP): src where it stores something (KEEP_EMPTY's content) */
+#define SVO_RULE_ERASE 8u    /* (KEEP, CLEAR, KEEP): carve src's silhouette out of dst */
+#define SVO_RULE_XOR 9u      /* (TAKE, CLEAR, KEEP): the symmetric difference */
+#define SVO_RULE_MASK 32u    /* (KEEP, KEEP, CLEAR): keep dst only inside src's silhouette */
+#define SVO_RULE_STENCIL 36u /* (KEEP, TAKE, CLEAR): src's ids inside the intersection, nothing else */
+#define SVO_RULE_REPLACE 37u /* (TAKE, TAKE, CLEAR): the box of src, empties included (REPLACE's content) */
+int svo_tree_patch_tree_rule_gpu(svo_tree* dst, const svo_tree* src, const svo_paste* p, uint32_t rule);
 /* node records and material entries superseded by edits (svo_tree_update, svo_tree_patch_volume_gpu,
-   svo_tree_patch_points_gpu, svo_tree_patch_shapes_gpu, svo_tree_patch_tree_gpu, svo_tree_patch_tree_oriented_gpu) since the last full build: still in the arrays, no longer reachable (either may be NULL) */
+   svo_tree_patch_points_gpu, svo_tree_patch_shapes_gpu, svo_tree_patch_tree_gpu, svo_tree_patch_tree_oriented_gpu,
+   svo_tree_patch_tree_rule_gpu) since the last full build: still in the arrays, no longer reachable (either may be NULL) */
 int svo_tree_garbage(const svo_tree* t, uint64_t* nodes, uint64_t* mats);
 /* diagnostics (tools/volume_patch_timing.py, tools/points_patch_timing.py): host-clock milliseconds of the tree's last
-   svo_tree_patch_volume_gpu, svo_tree_patch_points_gpu, svo_tree_patch_shapes_gpu or svo_tree_patch_tree_gpu, whichever ran last, after its entry
+   svo_tree_patch_volume_gpu, svo_tree_patch_points_gpu, svo_tree_patch_shapes_gpu or svo_tree_patch_tree_gpu (or its oriented
+   and rule forms), whichever ran last, after its entry
    synchronisation: ms[0] the device passes (volume: pyramid, count and write passes into scratch; points: keys, sort, edit
    list, column blocks, count and write passes; shapes and tree: the table's upload, the host's garbage walk, count and
    write passes), ms[1] the commit to the arrays and the copy back to the host image, ms[2] the host's ceiling update

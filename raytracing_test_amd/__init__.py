@@ -141,6 +141,24 @@ class PointsDesc(C.Structure):
 
 SHAPE_BOX, SHAPE_BALL = 0, 1
 PASTE_REPLACE, PASTE_KEEP_EMPTY = 0, 1   # svo_tree_patch_tree_gpu's and svo_paste's flags
+# svo_tree_patch_tree_rule_gpu's rules: what a voxel keeps where only src stores something (a), where both do (b) and where
+# only dst does (c)
+RULE_KEEP, RULE_TAKE, RULE_CLEAR = 0, 1, 2
+
+
+def paste_rule(a, b, c):
+    """SVO_RULE(a, b, c): a in (RULE_KEEP, RULE_TAKE), b any of the three, c in (RULE_KEEP, RULE_CLEAR)"""
+    return int(a) | int(b) << 2 | int(c) << 4
+
+
+RULE_UNDER = paste_rule(RULE_TAKE, RULE_KEEP, RULE_KEEP)       # fill only air
+RULE_PAINT = paste_rule(RULE_KEEP, RULE_TAKE, RULE_KEEP)       # recolour only what is solid
+RULE_OVER = paste_rule(RULE_TAKE, RULE_TAKE, RULE_KEEP)        # keep_empty's content
+RULE_ERASE = paste_rule(RULE_KEEP, RULE_CLEAR, RULE_KEEP)      # carve
+RULE_XOR = paste_rule(RULE_TAKE, RULE_CLEAR, RULE_KEEP)        # the symmetric difference
+RULE_MASK = paste_rule(RULE_KEEP, RULE_KEEP, RULE_CLEAR)       # keep dst only inside src's silhouette
+RULE_STENCIL = paste_rule(RULE_KEEP, RULE_TAKE, RULE_CLEAR)    # src's ids inside the intersection
+RULE_REPLACE = paste_rule(RULE_TAKE, RULE_TAKE, RULE_CLEAR)    # the plain paste's content
 
 
 class Paste(C.Structure):
@@ -217,6 +235,7 @@ ABI_SYMBOLS = (
     "svo_tree_patch_volume_gpu", "svo_tree_garbage", "svo_tree_patch_times", "svo_tree_compact_gpu", "svo_tree_compact_times",
     "svo_build_points_gpu", "svo_tree_get_blocks_gpu", "svo_tree_patch_points_gpu", "svo_tree_list_voxels_gpu",
     "svo_tree_diff_gpu", "svo_tree_patch_shapes_gpu", "svo_tree_patch_tree_gpu", "svo_tree_patch_tree_oriented_gpu",
+    "svo_tree_patch_tree_rule_gpu",
 )
 
 
@@ -309,7 +328,8 @@ def lib():
                      ("svo_tree_diff_gpu", [vp, vp, C.POINTER(i32), i32, i32, i32, vp, vp, C.c_int64, C.POINTER(C.c_int64), vp]),
                      ("svo_tree_patch_shapes_gpu", [vp, C.POINTER(Shape), i32]),
                      ("svo_tree_patch_tree_gpu", [vp, vp, C.POINTER(i32), i32, i32, i32, C.POINTER(i32), C.c_uint32]),
-                     ("svo_tree_patch_tree_oriented_gpu", [vp, vp, C.POINTER(Paste)])):
+                     ("svo_tree_patch_tree_oriented_gpu", [vp, vp, C.POINTER(Paste)]),
+                     ("svo_tree_patch_tree_rule_gpu", [vp, vp, C.POINTER(Paste), C.c_uint32])):
         if hasattr(L, name):
             getattr(L, name).argtypes = at
     L.svo_build_terrain.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
@@ -887,22 +907,13 @@ class Tree:
                "svo_tree_patch_tree_gpu")
         return self
 
-    def patch_tree_oriented(self, src, src_origin, dims, dst_origin, axis=(0, 1, 2), flip=(0, 0, 0), id_map=None, keep_empty=False):
-        """svo_tree_patch_tree_oriented_gpu: patch_tree() turned, mirrored and with its ids remapped.  The box of `dims` =
-        (nx, ny, nz) voxels at `src_origin` of the (uploaded) tree `src` (src_origin None: the whole of src) goes to
-        `dst_origin` of this (uploaded) tree with this tree's axis a running along src's axis axis[a], against it where
-        flip[a] is 1: the destination box has dims[axis[a]] voxels along a, and its voxel dst_origin + d reads src at s with
-        s[axis[a]] = src_origin[axis[a]] + (dims[axis[a]] - 1 - d[a] if flip[a] else d[a]).  Any of the 48 signed axis
-        permutations is valid.  id_map: None, or a sequence or array with one entry per entry of src's palette, each an id
-        of this tree's palette and id_map[0] == 0; src's id goes through it first, then keep_empty decides on the mapped id
-        (a material mapped to 0 is transparent with keep_empty, erases without), then an id this tree's view does not store
-        becomes empty.  With a map src's palette may be larger than this tree's.  Cost, self-paste and what is brought up
-        to date are patch_tree()'s."""
+    def _paste_struct(self, src, src_origin, dims, dst_origin, axis, flip, id_map, flags, who):
+        """the svo_paste of an oriented placement and the ctypes table it points to (keep the table alive over the call)"""
         if not isinstance(src, Tree):
             raise ValueError("src: a Tree")
         for t, name in ((self, "dst"), (src, "src")):
             if t.info().device < 0:
-                raise SvoError("svo_tree_patch_tree_oriented_gpu failed (-4): tree %s not uploaded (svo_upload)" % name)
+                raise SvoError("%s failed (-4): tree %s not uploaded (svo_upload)" % (who, name))
         if len(dst_origin) != 3 or len(axis) != 3 or len(flip) != 3:
             raise ValueError("dst_origin, axis, flip: three integers each")
         p = Paste()
@@ -914,7 +925,7 @@ class Tree:
         p.src_origin[:] = [int(v) for v in src_origin]
         p.n[:] = [int(v) for v in dims]
         p.dst_origin[:] = [int(v) for v in dst_origin]
-        p.flags = PASTE_KEEP_EMPTY if keep_empty else PASTE_REPLACE
+        p.flags = flags
         for name, vals in (("axis", axis), ("flip", flip)):
             vals = [int(v) for v in vals]
             if any(v < 0 or v > 255 for v in vals):
@@ -929,7 +940,41 @@ class Tree:
                 raise ValueError("id_map: ids are 0..65535")
             table = (C.c_uint16 * max(1, len(vals)))(*vals)
             p.id_map = C.cast(table, C.POINTER(C.c_uint16))
+        return p, table
+
+    def patch_tree_oriented(self, src, src_origin, dims, dst_origin, axis=(0, 1, 2), flip=(0, 0, 0), id_map=None, keep_empty=False):
+        """svo_tree_patch_tree_oriented_gpu: patch_tree() turned, mirrored and with its ids remapped.  The box of `dims` =
+        (nx, ny, nz) voxels at `src_origin` of the (uploaded) tree `src` (src_origin None: the whole of src) goes to
+        `dst_origin` of this (uploaded) tree with this tree's axis a running along src's axis axis[a], against it where
+        flip[a] is 1: the destination box has dims[axis[a]] voxels along a, and its voxel dst_origin + d reads src at s with
+        s[axis[a]] = src_origin[axis[a]] + (dims[axis[a]] - 1 - d[a] if flip[a] else d[a]).  Any of the 48 signed axis
+        permutations is valid.  id_map: None, or a sequence or array with one entry per entry of src's palette, each an id
+        of this tree's palette and id_map[0] == 0; src's id goes through it first, then keep_empty decides on the mapped id
+        (a material mapped to 0 is transparent with keep_empty, erases without), then an id this tree's view does not store
+        becomes empty.  With a map src's palette may be larger than this tree's.  Cost, self-paste and what is brought up
+        to date are patch_tree()'s."""
+        p, table = self._paste_struct(src, src_origin, dims, dst_origin, axis, flip, id_map, PASTE_KEEP_EMPTY if keep_empty else PASTE_REPLACE,
+                                      "svo_tree_patch_tree_oriented_gpu")
         _check(lib().svo_tree_patch_tree_oriented_gpu(self._h, src._h, C.byref(p)), "svo_tree_patch_tree_oriented_gpu")
+        del table
+        return self
+
+    def patch_tree_rule(self, src, src_origin, dims, dst_origin, rule, axis=(0, 1, 2), flip=(0, 0, 0), id_map=None):
+        """svo_tree_patch_tree_rule_gpu: patch_tree_oriented()'s placement (box, orientation, id map) under a rule that
+        asks both sides.  For every voxel of the destination box, s is src's mapped id and d the id this tree stores there
+        on entry, in this tree's own view; `rule` = paste_rule(a, b, c) says what the voxel holds afterwards where only src
+        stores something (a: RULE_KEEP leaves it empty, RULE_TAKE takes s), where both do (b: RULE_KEEP keeps d, RULE_TAKE
+        takes s, RULE_CLEAR empties it) and where only this tree does (c: RULE_KEEP or RULE_CLEAR).  RULE_UNDER fills only
+        air, RULE_PAINT recolours only what is solid, RULE_ERASE carves, RULE_XOR, RULE_MASK and RULE_STENCIL combine
+        silhouettes; RULE_OVER and RULE_REPLACE have the content of patch_tree_oriented() with and without keep_empty.  An
+        id this tree's view does not store becomes empty.  Because d is read in this tree's view, the solid-view and the
+        full-view tree of one world are not kept the two views of one world by a rule that depends on d.  The arrays are
+        never restarted; cost, self-paste and what is brought up to date are patch_tree()'s."""
+        p, table = self._paste_struct(src, src_origin, dims, dst_origin, axis, flip, id_map, 0, "svo_tree_patch_tree_rule_gpu")
+        rule = int(rule)
+        if rule < 0 or rule > 0xFFFFFFFF:
+            raise ValueError("rule: an unsigned 32-bit value")
+        _check(lib().svo_tree_patch_tree_rule_gpu(self._h, src._h, C.byref(p), rule), "svo_tree_patch_tree_rule_gpu")
         del table
         return self
 

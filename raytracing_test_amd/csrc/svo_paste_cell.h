@@ -8,6 +8,8 @@
 // child slot becomes, the host walk counts from it what the pass supersedes, and the two must agree on every cell.
 // The functions are written once, over the record type: PasteRec is the identity orientation and the identity map at
 // compile time (the plain paste's kernels carry neither), PasteTurn the general case.
+// svo_tree_patch_tree_rule_gpu's cell logic is at the end: PasteRule, a PasteTurn with a rule over both sides and dst's own
+// arrays, asked through rule_relation and rule_takes (tests/sanitize/paste_rule_plan_sanitize.cpp).
 // The arrays may be the host images or the copies in HBM; every node and material index is widened to 64 bits before it
 // addresses memory.
 #pragma once
@@ -194,6 +196,128 @@ template <class Rec>
 SVO_HD uint32_t paste_voxel(const Rec& R, const PasteTree& S, const PasteTree& D, int32_t x, int32_t y, int32_t z) {
     uint32_t id;
     return paste_takes(R, S, x, y, z, &id) ? id : tree_voxel(D, (uint32_t)x, (uint32_t)y, (uint32_t)z);
+}
+
+// svo_tree_patch_tree_rule_gpu: an oriented paste that decides every voxel from both sides.  s is src's mapped id (steps
+// (1) and (2) of the oriented paste), d the id dst stores at the voxel on entry, in dst's own view; `rule` holds, two bits
+// each, what the voxel keeps in the three cases that are not trivially empty (include/svo_rt.h SVO_RULE):
+//   A = rule & 3         s != 0, d == 0:  KEEP (stays empty) or TAKE (src's id, resolved against dst's view)
+//   B = (rule >> 2) & 3  s != 0, d != 0:  KEEP (d), TAKE or CLEAR (empty)
+//   C = (rule >> 4) & 3  s == 0, d != 0:  KEEP (d) or CLEAR
+// The record carries dst's arrays as they were on entry (the host images, or the copies in HBM, as src's): the patch is
+// written to scratch, so they do not change under the descent.  keep_empty is not read.
+enum : uint32_t { RULE_KEEP = 0u, RULE_TAKE = 1u, RULE_CLEAR = 2u };
+struct PasteRule : PasteTurn {
+    uint32_t rule;  // checked by the host (svo_plan.cpp paste_rule_check)
+    PasteTree dst;
+};
+
+// The aligned destination cell under a rule: paste_relation's three answers.  The src side is paste_relation's — the
+// clipped cell's ends mapped into src, the 2 x 2 x 2 src_cell walks through the id map: uniform 0, uniform id or mixed —
+// and the dst side is one more src_cell walk, over dst's arrays at the cell's own depth: a K_SOLID record at or above the
+// cell (uniform), a clear slot bit at or above it (empty), or a record at its level (mixed).  Nine walks of at most 7
+// dependent loads, the same trip count in every lane.
+//   OUT     the cell misses the box, or no voxel of its part of the box can change: src stores nothing there and C keeps
+//           (or dst is empty too); dst is empty and A keeps; src stores something throughout and dst's answer is kept
+//           whatever it is (dst uniform and B keeps, dst mixed and A and B keep); src is mixed and dst uniform, B and C
+//           keep.  All of them wherever the cell lies against the box;
+//   IN      the cell lies wholly inside the box and every voxel of it ends as *id: src is uniform, and so is dst, or the
+//           rule gives d == 0 and d != 0 the same outcome;
+//   CUT     everything else: the box's surface cuts the cell, a src record of its level overlaps it, or the outcome depends
+//           on d and dst holds a record of the cell's level under a non-empty src region.
+// Conservative as paste_relation is; a K_SOLID record of id 0, should one exist, reads as empty on either side.
+SVO_HD uint32_t rule_relation(const PasteRule& R, const PasteTree& S, int32_t x, int32_t y, int32_t z, int32_t cs, int k, uint32_t* id) {
+    const int32_t c[3] = {x, y, z};
+    bool out = false, in = true;
+    int32_t q0[3], q1[3];
+    for (int a = 0; a < 3; a++) {
+        out = out || c[a] + cs <= R.lo[a] || c[a] >= R.hi[a];
+        in = in && c[a] >= R.lo[a] && c[a] + cs <= R.hi[a];
+        const int32_t lo = c[a] > R.lo[a] ? c[a] : R.lo[a], hi = c[a] + cs < R.hi[a] ? c[a] + cs : R.hi[a];
+        q0[a] = lo;
+        q1[a] = hi - 1;
+    }
+    uint32_t a0[3] = {0u, 0u, 0u}, a1[3] = {0u, 0u, 0u};
+    paste_source(R, q0, a0);
+    paste_source(R, q1, a1);
+    *id = 0u;
+    if (out) return PASTE_OUT;
+    const int depth = k < S.levels ? S.levels - k : 0;
+    uint32_t first = 0u;
+    bool uni = true;
+    for (uint32_t i = 0; i < 8u; i++) {
+        const uint32_t u = paste_mapped(R, src_cell(S, depth, (i & 1u) ? a1[0] : a0[0], (i & 2u) ? a1[1] : a0[1], (i & 4u) ? a1[2] : a0[2]));
+        first = i == 0u ? u : first;
+        uni = uni && u != kPasteMixed && u == first;
+    }
+    // the cell itself in dst (k <= dst's levels - 1: the descent starts below the root)
+    const uint32_t d = src_cell(R.dst, R.dst.levels - k, (uint32_t)x, (uint32_t)y, (uint32_t)z);
+    const uint32_t A = R.rule & 3u, B = (R.rule >> 2) & 3u, C = (R.rule >> 4) & 3u;
+    const bool d_empty = d == 0u, d_uni = d != 0u && d != kPasteMixed;
+    const uint32_t took = uni ? paste_resolve(R, first) : 0u;
+    if (uni && first == 0u) {
+        if (C == RULE_KEEP || d_empty) return PASTE_OUT;
+        return in ? PASTE_IN : PASTE_CUT;  // cleared
+    }
+    if (d_empty) {
+        if (A == RULE_KEEP) return PASTE_OUT;
+        *id = took;
+        return uni && in ? PASTE_IN : PASTE_CUT;
+    }
+    if (!uni) return d_uni && B == RULE_KEEP && C == RULE_KEEP ? PASTE_OUT : PASTE_CUT;
+    if (d_uni) {
+        if (B == RULE_KEEP) return PASTE_OUT;
+        *id = B == RULE_TAKE ? took : 0u;
+        return in ? PASTE_IN : PASTE_CUT;
+    }
+    // dst mixed under one src id: decided at the cell only where d == 0 and d != 0 end alike
+    if (A == RULE_KEEP && B == RULE_KEEP) return PASTE_OUT;
+    if (A == RULE_TAKE && B == RULE_TAKE) {
+        *id = took;
+        return in ? PASTE_IN : PASTE_CUT;
+    }
+    if (A == RULE_KEEP && B == RULE_CLEAR) return in ? PASTE_IN : PASTE_CUT;
+    return PASTE_CUT;
+}
+
+// one destination voxel under a rule: true when the rule changes or decides it, *id then what dst stores there.  d is
+// read from dst's arrays as they were on entry
+SVO_HD bool rule_takes(const PasteRule& R, const PasteTree& S, int32_t x, int32_t y, int32_t z, uint32_t* id) {
+    *id = 0u;
+    if (x < R.lo[0] || x >= R.hi[0] || y < R.lo[1] || y >= R.hi[1] || z < R.lo[2] || z >= R.hi[2]) return false;
+    const int32_t q[3] = {x, y, z};
+    uint32_t p[3] = {0u, 0u, 0u};
+    paste_source(R, q, p);
+    const uint32_t s = paste_mapped(R, tree_voxel(S, p[0], p[1], p[2]));
+    const uint32_t d = tree_voxel(R.dst, (uint32_t)x, (uint32_t)y, (uint32_t)z);
+    if (s == 0u) return d != 0u && ((R.rule >> 4) & 3u) == RULE_CLEAR;
+    const uint32_t f = d == 0u ? R.rule & 3u : (R.rule >> 2) & 3u;
+    if (f == RULE_KEEP) return false;
+    *id = f == RULE_TAKE ? paste_resolve(R, s) : 0u;
+    return true;
+}
+
+// the composite voxel after a rule paste
+SVO_HD uint32_t rule_voxel(const PasteRule& R, const PasteTree& S, int32_t x, int32_t y, int32_t z) {
+    uint32_t id;
+    return rule_takes(R, S, x, y, z, &id) ? id : tree_voxel(R.dst, (uint32_t)x, (uint32_t)y, (uint32_t)z);
+}
+
+// The question a record asks of a cell and of a voxel, by record type: the patch's device class and the host's garbage
+// walk are written once over these
+template <class Rec>
+SVO_HD uint32_t relation_of(const Rec& R, const PasteTree& S, int32_t x, int32_t y, int32_t z, int32_t cs, int k, uint32_t* id) {
+    return paste_relation(R, S, x, y, z, cs, k, id);
+}
+SVO_HD uint32_t relation_of(const PasteRule& R, const PasteTree& S, int32_t x, int32_t y, int32_t z, int32_t cs, int k, uint32_t* id) {
+    return rule_relation(R, S, x, y, z, cs, k, id);
+}
+template <class Rec>
+SVO_HD bool takes_of(const Rec& R, const PasteTree& S, int32_t x, int32_t y, int32_t z, uint32_t* id) {
+    return paste_takes(R, S, x, y, z, id);
+}
+SVO_HD bool takes_of(const PasteRule& R, const PasteTree& S, int32_t x, int32_t y, int32_t z, uint32_t* id) {
+    return rule_takes(R, S, x, y, z, id);
 }
 
 }  // namespace svo

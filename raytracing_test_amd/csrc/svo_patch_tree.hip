@@ -15,6 +15,11 @@
 // (svo_plan.cpp patch_anchor over the destination box), whose record is the only one rewritten in place; a REPLACE paste
 // over the whole extent restarts the arrays (the volume patch's rule).  The superseded records are counted by a host walk
 // (svo_plan.cpp paste_superseded) that asks the same paste_relation about the same cells over the two host images.
+// svo_tree_patch_tree_rule_gpu is the oriented paste under a rule that also asks what dst holds (svo_paste_cell.h PasteRule,
+// rule_relation, rule_takes): a ninth walk per cell, over dst's own arrays at the cell's depth, and per voxel of a cut brick
+// a second lookup, in dst.  The arrays it reads are dst's as they were on entry, since the patch is written to scratch.  It
+// never restarts the arrays.  Its kernels are four more instances of svo_patch_cells.h's (DevPasteRule); the other
+// instances do not change.
 // Every node and material index is widened to 64 bits before it addresses memory.
 #include <hip/hip_runtime.h>
 
@@ -36,19 +41,24 @@ namespace {
 // the patch as svo_patch_cells.h's kernels ask it, over the record type of the cell logic
 template <class Rec>
 struct DevPasteOf {
-    Rec rec;  // (in_view, id_map: the tables in HBM, or NULL)
+    Rec rec;  // (in_view, id_map: the tables in HBM, or NULL); the cell and the voxel ask through relation_of / takes_of
     PasteTree src;
     const Node* nodes;  // dst (read only: the patch is written to scratch)
     const uint16_t* mats;
     int32_t levels;
     uint64_t nbase;  // scratch record s >= 1 becomes node nbase + s - 1 of dst
     __device__ uint32_t relation(int32_t x, int32_t y, int32_t z, int32_t cs, int k, uint32_t* id) const {
-        return paste_relation(rec, src, x, y, z, cs, k, id);
+        return relation_of(rec, src, x, y, z, cs, k, id);
     }
-    __device__ bool voxel(int32_t x, int32_t y, int32_t z, uint32_t* id) const { return paste_takes(rec, src, x, y, z, id); }
+    __device__ bool voxel(int32_t x, int32_t y, int32_t z, uint32_t* id) const { return takes_of(rec, src, x, y, z, id); }
 };
 struct DevPaste : DevPasteOf<PasteRec> {};      // svo_tree_patch_tree_gpu
 struct DevPasteTurn : DevPasteOf<PasteTurn> {};  // svo_tree_patch_tree_oriented_gpu
+struct DevPasteRule : DevPasteOf<PasteRule> {};  // svo_tree_patch_tree_rule_gpu (rec.dst: dst's arrays in HBM, as nodes and mats)
+
+// dst's arrays into the record, where the cell logic reads them
+void set_dst(PasteRec&, const PasteTree&) {}
+void set_dst(PasteRule& rec, const PasteTree& dst) { rec.dst = dst; }
 
 // the id map (a host array of n entries) to the device, where the record has one
 int upload_id_map(Pool&, PasteRec&, size_t) { return SVO_OK; }
@@ -114,6 +124,7 @@ int paste_run(svo_tree* dst, const svo_tree* src, const char* who, const Rec& re
     if (!whole) {
         Rec hrec = rec;
         hrec.in_view = all ? nullptr : bits.data();
+        set_dst(hrec, PasteTree{dst->nodes.data(), dst->mats.data(), L});
         paste_superseded(dst->nodes.data(), L, anchor, hrec, PasteTree{src->nodes.data(), src->mats.data(), src->levels}, &gnodes, &gmats);
     }
 
@@ -125,6 +136,7 @@ int paste_run(svo_tree* dst, const svo_tree* src, const char* who, const Rec& re
            reinterpret_cast<const uint16_t*>(dst->d_mats),
            L,
            nbase}};
+    set_dst(P.rec, PasteTree{P.nodes, P.mats, L});
     if (!all) {
         uint32_t* dbits;
         rc = pool.alloc(&dbits, bits.size());
@@ -189,4 +201,39 @@ extern "C" int svo_tree_patch_tree_oriented_gpu(svo_tree* dst, const svo_tree* s
     if (rc) return rc;
     plan.rec.id_map = p->id_map;
     return paste_run<DevPasteTurn, PasteTurn>(dst, src, who, plan.rec, plan.whole);
+}
+
+extern "C" int svo_tree_patch_tree_rule_gpu(svo_tree* dst, const svo_tree* src, const svo_paste* p, uint32_t rule) {
+    const char* who = "svo_tree_patch_tree_rule_gpu";
+    if (!dst || !src) SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_rule_gpu: NULL tree");
+    if (!p) SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_rule_gpu: NULL svo_paste");
+    switch (paste_rule_check(p->flags, rule)) {
+        case RULE_FLAGS: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_rule_gpu: svo_paste's flags must be 0 (the rule replaces them)");
+        case RULE_BITS: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_rule_gpu: unknown rule bits (a rule is SVO_RULE(a, b, c), below 64)");
+        case RULE_SRC_ONLY: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_rule_gpu: the rule's src-only case must be SVO_RULE_KEEP or SVO_RULE_TAKE");
+        case RULE_BOTH: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_rule_gpu: the rule's both case must be SVO_RULE_KEEP, SVO_RULE_TAKE or SVO_RULE_CLEAR");
+        case RULE_DST_ONLY: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_rule_gpu: the rule's dst-only case must be SVO_RULE_KEEP or SVO_RULE_CLEAR");
+        default: break;
+    }
+    PastePlan plan;
+    switch (paste_plan(dst->levels, src->levels, p->src_origin, p->n[0], p->n[1], p->n[2], p->dst_origin, 0u, &plan, p->axis, p->flip)) {
+        case PASTE_AXIS: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_rule_gpu: axis must be a permutation of 0, 1, 2");
+        case PASTE_FLIP: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_rule_gpu: flip entries must be 0 or 1");
+        case PASTE_DIM: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_rule_gpu: the box's dimensions must be positive");
+        case PASTE_SRC_EXTENT: SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_rule_gpu: the source box must lie within src's extent (no wrap)");
+        case PASTE_DST_EXTENT:
+            SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_rule_gpu: the destination box (the dimensions permuted by axis) must lie within dst's extent (no wrap)");
+        default: break;
+    }
+    if (p->id_map && !src->palette.empty() && p->id_map[0] != 0) SVO_FAIL(SVO_EINVAL, "svo_tree_patch_tree_rule_gpu: id_map[0] must be 0");
+    const int rc = paste_check_trees(dst, src, who, p->id_map);
+    if (rc) return rc;
+    if (rule == 0u) return SVO_OK;  // every case keeps: nothing to do
+    PasteRule rec;
+    static_cast<PasteTurn&>(rec) = plan.rec;
+    rec.id_map = p->id_map;
+    rec.keep_empty = 0u;
+    rec.rule = rule;
+    rec.dst = PasteTree{nullptr, nullptr, dst->levels};
+    return paste_run<DevPasteRule, PasteRule>(dst, src, who, rec, false);  // (never a restart: svo_tree_compact_gpu exists)
 }

@@ -561,6 +561,16 @@ int paste_plan(int32_t dst_levels, int32_t src_levels, const int32_t* src_origin
     return PASTE_OK;
 }
 
+int paste_rule_check(uint32_t flags, uint32_t rule) {
+    if (flags) return RULE_FLAGS;
+    if (rule >> 6) return RULE_BITS;
+    const uint32_t A = rule & 3u, B = (rule >> 2) & 3u, C = (rule >> 4) & 3u;
+    if (A != RULE_KEEP && A != RULE_TAKE) return RULE_SRC_ONLY;
+    if (B > RULE_CLEAR) return RULE_BOTH;
+    if (C != RULE_KEEP && C != RULE_CLEAR) return RULE_DST_ONLY;
+    return RULE_OK;
+}
+
 bool paste_view_bits(const std::vector<Material>& palette, int32_t view, std::vector<uint32_t>* bits) {
     bits->assign((palette.size() + 31) / 32, 0u);
     bool all = true;
@@ -578,7 +588,7 @@ void paste_superseded_as(const Node* nodes, int32_t levels, const PatchAnchor& a
                          uint64_t* n_mats) {
     auto rel = [&](const int32_t co[3], int32_t cs, int k) {
         uint32_t id;
-        return paste_relation(rec, src, co[0], co[1], co[2], cs, k, &id);
+        return relation_of(rec, src, co[0], co[1], co[2], cs, k, &id);
     };
     CellSuperseded<decltype(rel)> s{nodes, levels, rel};
     s.walk(a.node, a.o, a.depth, false);
@@ -593,6 +603,11 @@ void paste_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, c
 }
 
 void paste_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const PasteTurn& rec, const PasteTree& src, uint64_t* n_nodes,
+                      uint64_t* n_mats) {
+    paste_superseded_as(nodes, levels, a, rec, src, n_nodes, n_mats);
+}
+
+void paste_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const PasteRule& rec, const PasteTree& src, uint64_t* n_nodes,
                       uint64_t* n_mats) {
     paste_superseded_as(nodes, levels, a, rec, src, n_nodes, n_mats);
 }

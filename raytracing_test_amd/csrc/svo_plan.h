@@ -149,6 +149,19 @@ struct PastePlan {
 };
 int paste_plan(int32_t dst_levels, int32_t src_levels, const int32_t* src_origin, int32_t nx, int32_t ny, int32_t nz, const int32_t dst_origin[3],
                uint32_t flags, PastePlan* plan, const uint8_t* axis = nullptr, const uint8_t* flip = nullptr);
+// svo_tree_patch_tree_rule_gpu (svo_patch_tree.hip) is the oriented paste under a rule over both sides (svo_paste_cell.h
+// PasteRule).  Its geometry is paste_plan's with flags 0; the rule has a check and statuses of its own, in the order of
+// the list: svo_paste's flags must be 0 (the rule replaces them), no bit above 5, A is KEEP or TAKE, B any of the three,
+// C is KEEP or CLEAR
+enum : int {
+    RULE_OK = 0,
+    RULE_FLAGS = 1,     // svo_paste.flags is not 0
+    RULE_BITS = 2,      // a bit above 5
+    RULE_SRC_ONLY = 3,  // A is CLEAR or 3
+    RULE_BOTH = 4,      // B is 3
+    RULE_DST_ONLY = 5,  // C is TAKE or 3
+};
+int paste_rule_check(uint32_t flags, uint32_t rule);
 // the in-view bit table of a palette under `view` (bit id: the view stores the id; bit 0 is set: id 0 stays 0); returns
 // true when every id is in view
 bool paste_view_bits(const std::vector<Material>& palette, int32_t view, std::vector<uint32_t>* bits);
@@ -157,6 +170,9 @@ bool paste_view_bits(const std::vector<Material>& palette, int32_t view, std::ve
 void paste_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const PasteRec& rec, const PasteTree& src, uint64_t* n_nodes,
                       uint64_t* n_mats);
 void paste_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const PasteTurn& rec, const PasteTree& src, uint64_t* n_nodes,
+                      uint64_t* n_mats);
+// the same walk with rule_relation asked (rec.dst: dst's host image, the array `nodes` belongs to)
+void paste_superseded(const Node* nodes, int32_t levels, const PatchAnchor& a, const PasteRule& rec, const PasteTree& src, uint64_t* n_nodes,
                       uint64_t* n_mats);
 
 // svo_tree_list_voxels_gpu (svo_list_voxels.hip) lists the voxels inside a box of the extent 4^levels: origin == NULL is the

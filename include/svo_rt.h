@@ -614,6 +614,13 @@ int svo_tree_device_ceilings(const svo_tree* t, int16_t* ceil, uint32_t* pairs, 
    level (4^SVO_CEIL_K0 columns, row-major [z][x]), the ceilings of the blocks of levels 0..3 holding it, int16 each,
    level j in bits 16j..16j+15 (a level the tree lacks: 0x7FFF).  quads may be NULL (count only); n = elements. */
 int svo_tree_device_ceiling_quads(const svo_tree* t, uint64_t* quads, int64_t cap, int64_t* n);
+/* The fine ceilings, one level below svo_tree_ceilings' finest: per aligned block of 4^(SVO_CEIL_K0 - 1) columns (one
+   brick's footprint) the highest stored voxel row (-1: none), int16 row-major [z][x]; shift = log2 of the block's
+   width.  The march before the traversal loop descends onto them.  A tree without ceiling levels has none (n = 0).
+   2 bytes per 16 columns: 2 MB for a 4096-voxel world, 32 MB for a 16384-voxel one.  svo_tree_ceilings_fine computes
+   them from the host tree; svo_tree_device_ceilings_fine reads the table in HBM.  out / fine may be NULL (count only). */
+int svo_tree_ceilings_fine(const svo_tree* t, int16_t* out, int64_t cap, int32_t* shift, int64_t* n);
+int svo_tree_device_ceilings_fine(const svo_tree* t, int16_t* fine, int64_t cap, int64_t* n);
 /* The frame schedule of (hip_stream, kind: 2 shading; 0 / 1, primary and AO casts, keep none) over t (inspection /
    tests; SVO_CAST_NO_SCHEDULE): the dispatch order of the next frames of that geometry, by groups of SVO_SCHED_GROUP
    consecutive blocks (order[slot group] = frame group; n / SVO_SCHED_GROUP entries) and the block durations of the frame

@@ -52,6 +52,9 @@ STAT_NAMES = ("rays", "lookups", "node_loads", "skips", "skip_budget_out", "bric
               "wave_iters", "wave_brick_steps",
               "no_progress", "root_starts", "cache_empty", "wave_skips", "wave_descents",
               "path_starts", "ao_node_loads", "ceil_moves", "iters_above_top", "bends", "tints", "tint_iters")  # wave_*: per wave (64 rays)
+# the fine march's counters, in the slots after STAT_NAMES' (the second S_* enum of csrc/svo_stats.h): 4-column blocks the
+# march before the loop passed, and its descents from 16-column blocks onto them; cast_stats() returns them with the others
+MARCH_STAT_NAMES = ("march_fine", "march_descents")
 STATS_HEADER = 32  # u64 counters before the per-block stamps (SVO_STATS_HEADER)
 MAX_FRAMES = 16  # SVO_MAX_FRAMES: frames in one launch
 WIRE_BYTES = 12  # SVO_WIRE_BYTES: the larger wire record (12 B general, 8 B compact: Tree.wire_bytes(desc))
@@ -235,7 +238,7 @@ ABI_SYMBOLS = (
     "svo_tree_patch_volume_gpu", "svo_tree_garbage", "svo_tree_patch_times", "svo_tree_compact_gpu", "svo_tree_compact_times",
     "svo_build_points_gpu", "svo_tree_get_blocks_gpu", "svo_tree_patch_points_gpu", "svo_tree_list_voxels_gpu",
     "svo_tree_diff_gpu", "svo_tree_patch_shapes_gpu", "svo_tree_patch_tree_gpu", "svo_tree_patch_tree_oriented_gpu",
-    "svo_tree_patch_tree_rule_gpu",
+    "svo_tree_patch_tree_rule_gpu", "svo_tree_ceilings_fine", "svo_tree_device_ceilings_fine",
 )
 
 
@@ -312,6 +315,8 @@ def lib():
                      ("svo_tree_guard_trips", [vp, C.POINTER(C.c_uint64), i32]),
                      ("svo_tree_device_ceilings", [vp, vp, vp, C.c_int64, C.POINTER(i32), C.POINTER(C.c_int64)]),
                      ("svo_tree_device_ceiling_quads", [vp, vp, C.c_int64, C.POINTER(C.c_int64)]),
+                     ("svo_tree_ceilings_fine", [vp, vp, C.c_int64, C.POINTER(i32), C.POINTER(C.c_int64)]),
+                     ("svo_tree_device_ceilings_fine", [vp, vp, C.c_int64, C.POINTER(C.c_int64)]),
                      ("svo_tree_schedule", [vp, vp, C.c_int32, vp, vp, C.c_int64, C.POINTER(C.c_int64)]),
                      ("svo_cast_ray_from_cam_async", [vp, f3, f3, i32, vp, vp]),
                      ("svo_build_volume_gpu", [C.POINTER(VolumeDesc), C.POINTER(vp)]),
@@ -1162,6 +1167,30 @@ class Tree:
             off += rows * rows
         return res
 
+    def ceilings_fine(self):
+        """the fine ceilings of the host tree (svo_tree_ceilings_fine): one (E / 4^(CEIL_K0 - 1))^2 int16 array [z][x], one
+        level below ceilings()'s finest; None for a tree without ceiling levels"""
+        sh, n = C.c_int32(), C.c_int64()
+        _check(lib().svo_tree_ceilings_fine(self._h, None, 0, C.byref(sh), C.byref(n)), "svo_tree_ceilings_fine")
+        if n.value == 0:
+            return None
+        out = np.zeros(n.value, np.int16)
+        _check(lib().svo_tree_ceilings_fine(self._h, out.ctypes.data_as(C.c_void_p), n.value, C.byref(sh), C.byref(n)), "svo_tree_ceilings_fine")
+        rows = (1 << (2 * self.info().levels)) >> sh.value
+        assert rows * rows == n.value
+        return out.reshape(rows, rows)
+
+    def device_ceilings_fine(self):
+        """the fine ceilings in HBM as the march reads them (svo_tree_device_ceilings_fine), shaped as ceilings_fine(); None: none"""
+        n = C.c_int64()
+        _check(lib().svo_tree_device_ceilings_fine(self._h, None, 0, C.byref(n)), "svo_tree_device_ceilings_fine")
+        if n.value == 0:
+            return None
+        out = np.zeros(n.value, np.int16)
+        _check(lib().svo_tree_device_ceilings_fine(self._h, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)), "svo_tree_device_ceilings_fine")
+        rows = int(round(n.value ** 0.5))
+        return out.reshape(rows, rows)
+
     def wire_bytes(self, desc):
         """bytes per wire record of desc's records: 8 (compact: frames from integral / half-integral camera
         positions) or 12 (include/svo_rt.h)"""
@@ -1227,8 +1256,9 @@ class Tree:
         out = self.alloc_hits(n, dev)
         self.cast(d, out)
         _check(lib().svo_sync(None), "svo_sync")
-        v = st[:len(STAT_NAMES)].cpu().numpy().astype(np.float64)
-        return {k: v[i] / max(1.0, v[0]) for i, k in enumerate(STAT_NAMES)}
+        names = STAT_NAMES + MARCH_STAT_NAMES
+        v = st[:len(names)].cpu().numpy().astype(np.float64)
+        return {k: v[i] / max(1.0, v[0]) for i, k in enumerate(names)}
 
     def device_ceilings(self):
         """(levels, int16 ceilings, uint32 pairs) of the tables in HBM (svo_tree_device_ceilings)"""

@@ -181,6 +181,7 @@ static void set_ceilings(const svo_tree* t, const svo_cast_desc* d, CastParams& 
     // at least as high as that block's own, which is safe)
     P.ceilp = P.ceil_levels > 0 ? reinterpret_cast<const uint32_t*>(t->d_ceilp) + t->ceilp_off[lv[0]] : nullptr;
     P.ceilq = P.ceil_levels > 0 ? reinterpret_cast<const uint64_t*>(t->d_ceilq) : nullptr;
+    P.ceilf = ceil_fine_for(P.ceil_levels, lv[0]) ? reinterpret_cast<const int16_t*>(t->d_ceilf) : nullptr;
     for (int j = 0; j < 2; j++) {
         // (one level only: the second is a copy of the first, so the kernel may read both unconditionally)
         const int l = j < P.ceil_levels ? lv[j] : lv[0];
@@ -565,6 +566,17 @@ extern "C" int svo_tree_device_ceiling_quads(const svo_tree* t, uint64_t* quads,
     if (*n == 0 || !quads) return SVO_OK;
     HIP_TRY(hipSetDevice(t->device), SVO_EDEVICE);
     HIP_TRY(hipMemcpy(quads, t->d_ceilq, *n * sizeof(uint64_t), hipMemcpyDeviceToHost), SVO_EDEVICE);
+    return SVO_OK;
+}
+
+extern "C" int svo_tree_device_ceilings_fine(const svo_tree* t, int16_t* fine, int64_t cap, int64_t* n) {
+    if (!t || !n) SVO_FAIL(SVO_EINVAL, "svo_tree_device_ceilings_fine: NULL argument");
+    if (t->device < 0) SVO_FAIL(SVO_ESTATE, "svo_tree_device_ceilings_fine: tree not uploaded (svo_upload)");
+    *n = t->ceil_levels > 0 && t->d_ceilf ? (int64_t)t->ceil_fine_host.size() : 0;
+    if (fine && cap < *n) SVO_FAIL(SVO_ERANGE, "svo_tree_device_ceilings_fine: buffer too small");
+    if (*n == 0 || !fine) return SVO_OK;
+    HIP_TRY(hipSetDevice(t->device), SVO_EDEVICE);
+    HIP_TRY(hipMemcpy(fine, t->d_ceilf, *n * sizeof(int16_t), hipMemcpyDeviceToHost), SVO_EDEVICE);
     return SVO_OK;
 }
 

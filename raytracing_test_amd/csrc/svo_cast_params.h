@@ -84,6 +84,9 @@ struct CastParams {
     const uint32_t* sceilp;  // shading: the same pairs of the solid-view tree the shadow rays walk (trace T_CEIL_SHADOW)
     int32_t sceil_levels;
     const uint64_t* ceilq;  // every level per finest block (svo_tree.d_ceilq; trace CEIL == 2)
+    // the fine ceilings of the tree the rays walk (svo_tree.d_ceilf: 4-column blocks, row-major), which the march before
+    // the loop descends onto (ceil_march); null: none, or the launch's first level is not the table's finest
+    const int16_t* ceilf;
     uint32_t* guard_trips;  // the tree's counter of progress-guard trips (svo_tree_guard_trips)
     // frame schedule (sched_attach): launch block b casts frame block sched_order[b] (null: b) and, with sched_cost,
     // writes its duration (100 MHz ticks) to sched_cost[frame block]

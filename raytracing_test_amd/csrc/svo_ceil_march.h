@@ -4,14 +4,22 @@
 #pragma once
 
 #include "svo_exact.h"
+#include "svo_skip.h"
 #include "svo_stats.h"
+
+// the fine phase's bound, in 4-column blocks: the whole wave walks as far as its longest lane, so a ray gliding over a plain
+// must hand over to the loop's boxes (C3, interleaved on one box: 8 blocks 0.1368 ms, 24 0.1308, 64 0.1344)
+constexpr int32_t kMarchFineMax = 24;
+// ... and the budget it wants left beyond the first phase's end: its blocks span up to 8 x / z steps each.  A march whose end
+// lies beyond the budget moves nothing (skip_box refuses it), so a ray with less left keeps the first phase's end
+constexpr int32_t kMarchFineSpan = 8 * kMarchFineMax;
 
 // Column-ceiling march (round 5).  A descending ray above the ceiling of its 16-column block crosses, cell by cell,
 // only empty voxels until its row reaches that ceiling or it leaves the block; castRayFromCam's DDA (ray_caster.cpp:71-80)
 // takes its x / z / y steps at the crossing values T_k + j * a_k, so every event that matters here is one fma of an
 // integer index: the x (z) event entering the next block, j = the cells left in the block on that axis, and the y event
 // entering the ceiling row c, j = y - 1 - c.  The march walks the blocks the ray's column path crosses (their order
-// follows from the x / z boundary events alone) comparing exact event values, one 32-bit ceiling load per block (the
+// follows from the x / z boundary events alone) comparing exact event values, one ceiling load per block (the
 // next block's load issued before this one is judged), until the ceiling event comes first or the ray enters a block
 // at or below its ceiling; every voxel entered before that event is then empty, and one closed-form crossing
 // (skip_box) moves the ray to the state right after it — the cell that event enters is the loop's next untested
@@ -19,32 +27,43 @@
 // each a full iteration with its own exact crossing) by one crossing and a few integer / fma steps per block.
 // Linear rays only (every sum exact: `fast` in the non-segment instances), stepping down (R.s[1] < 0); a tie between
 // the x and z boundary events (a block corner) or between a boundary and the ceiling event stops the march there.
-// Returns whether the ray moved.
-// The march's end: ex (skip_box's exits) of the first event whose voxel it could not prove empty.  Returns false when
-// nothing beyond the current voxel is proven (its own row is at or below its block's ceiling).
-template <bool STATS>
-__device__ __forceinline__ bool ceil_march(const CastParams& P, const uint32_t* __restrict__ ceilp, const Ray& R, uint32_t wm, int32_t ex[3],
-                                           Stats& st) {
-    const uint32_t lsh = P.ceil_sh[0];  // the finest level's blocks: 2^lsh columns
-    const uint32_t bm = (1u << lsh) - 1u, rows = (wm + 1u) >> lsh, rm = rows - 1u;
-    const int32_t wy = (int32_t)((uint32_t)R.r[1] & wm);
-    const uint32_t wx = (uint32_t)R.r[0] & wm, wz = (uint32_t)R.r[2] & wm;
-    // per axis the next block-boundary event: its index from the current state (the cells left in the block) and value
-    int32_t jx = (int32_t)(R.s[0] > 0 ? bm - (wx & bm) : (wx & bm)), jz = (int32_t)(R.s[2] > 0 ? bm - (wz & bm) : (wz & bm));
-    double Ex = on_grid(R.T[0], jx, R.a(0)), Ez = on_grid(R.T[2], jz, R.a(2));
-    uint32_t bx = wx >> lsh, bz = wz >> lsh;
+
+// The march's state between blocks of one level: per axis the index (from the ray's state) and value of the event that
+// leaves the current block (bx, bz); the event that entered it (Ein: -inf, axis -1 for the block the ray starts in); and,
+// once a block fails, the first event whose voxel is not proven empty (stop_axis -1: the ray's own voxel)
+struct March {
+    int32_t jx, jz;
+    double Ex, Ez;
+    uint32_t bx, bz;
+    double Ein;
+    int32_t ein_axis, ein_j, stop_axis, stop_j;
+    int32_t jy;  // the index of the y event entering the ceiling row of the block that failed (negative: the ray entered below it)
+};
+
+// An upper estimate of the DDA steps up to the march's end: no more x (z) events than the failed block's exit index, no
+// more y events than down to its ceiling row (from below it: the rows down to 0).  Only what the march does with its
+// budget rests on it, never a result.
+__device__ __forceinline__ int32_t march_reach(const March& m, int32_t wy) { return m.jx + m.jz + 2 + (m.jy >= 0 ? m.jy : wy) + 1; }
+
+// The blocks of one level, 2^lsh columns wide, `rows` of them per row of the table ceil(index) reads, until one fails or
+// `bound` blocks are proven.  FINE only names the counter.
+template <bool STATS, bool FINE, class Ceil>
+__device__ __forceinline__ void march_level(const Ray& R, int32_t wy, uint32_t lsh, uint32_t rows, int32_t bound, const Ceil& ceil, March& m,
+                                            Stats& st) {
+    const uint32_t bm = (1u << lsh) - 1u, rm = rows - 1u;
     const uint32_t dx = R.s[0] > 0 ? 1u : rm, dz = R.s[2] > 0 ? 1u : rm;  // (one block on, wrapped)
-    uint32_t cv = ceilp[__umul24(bz, rows) + bx];
-    double Ein = -__builtin_inf();  // the event that entered the current block (none for the first)
-    int32_t ein_axis = -1, ein_j = 0, stop_axis = -1, stop_j = 0;
+    int32_t jx = m.jx, jz = m.jz, ein_axis = m.ein_axis, ein_j = m.ein_j, stop_axis = -1, stop_j = 0;
+    double Ex = m.Ex, Ez = m.Ez, Ein = m.Ein;
+    uint32_t bx = m.bx, bz = m.bz;
+    int32_t cv = ceil(__umul24(bz, rows) + bx), jy = 0;
     for (int32_t it = 0;; it++) {
         const bool xn = Ex < Ez;
         // the next block's ceiling, loaded before this block is judged (the blocks' order follows from x / z alone)
         const uint32_t nbx = xn ? (bx + dx) & rm : bx, nbz = xn ? bz : (bz + dz) & rm;
-        const uint32_t ncv = ceilp[__umul24(nbz, rows) + nbx];
-        const int32_t jy = wy - 1 - (int32_t)(int16_t)(cv & 0xFFFFu);  // the y event entering the ceiling row
+        const int32_t ncv = ceil(__umul24(nbz, rows) + nbx);
+        jy = wy - 1 - cv;  // the y event entering the ceiling row
         const double tc = jy >= 0 ? on_grid(R.T[1], jy, R.a(1)) : -__builtin_inf();
-        if (!(tc > Ein) || it == 1024) {  // the voxel entering this block is at or below its ceiling: end before that event
+        if (!(tc > Ein) || it == bound) {  // the voxel entering this block is at or below its ceiling: end before that event
             stop_axis = ein_axis;        // (and a bound on the march: its blocks so far are proven)
             stop_j = ein_j;
             break;
@@ -65,7 +84,10 @@ __device__ __forceinline__ bool ceil_march(const CastParams& P, const uint32_t* 
             }
             break;
         }
-        if (STATS) st.ceil_moves++;
+        if (STATS) {
+            if (FINE) st.march_fine++;
+            else st.ceil_moves++;
+        }
         Ein = Eexit;  // on into the next block
         if (xn) {
             ein_axis = 0;
@@ -82,9 +104,69 @@ __device__ __forceinline__ bool ceil_march(const CastParams& P, const uint32_t* 
         bz = nbz;
         cv = ncv;
     }
+    m = March{jx, jz, Ex, Ez, bx, bz, Ein, ein_axis, ein_j, stop_axis, stop_j, jy};
+}
+
+// The march: over the 16-column blocks of the launch's first ceiling level (ceilp: its pairs), then — fine descent — over
+// 4-column blocks on the tree's fine ceilings (ceilf: svo_tree.d_ceilf, int16 row-major; null: none).  A 16-column block's
+// ceiling is the maximum over 256 columns, far above most of them on terrain, so the first phase ends long before the ray
+// meets anything: it enters a block at or below its ceiling, or that block's ceiling event comes before its exit.  The
+// second phase takes the march on from the event that entered that block, judging 4-column blocks the same way, through
+// as many 16-column blocks as it takes, for at most kMarchFineMax blocks (what it has proven by then stands; the loop's
+// ceiling boxes carry on), and only for rays with kMarchFineSpan steps of budget to spare beyond the first phase's end.
+// The 4-column block the ray is in at the entering event follows from the cells it has left in
+// the 16-column block on each axis: on the axis it entered by, all of them; on the other, the exit index less the events
+// of that axis that precede the entering event in the DDA's order (z before x at equal values), counted exactly (count_est
+// and its settling compare, as skip_box counts them).  Two loops, not one over blocks of either size: a wave runs each
+// until its last lane is done, and a loop that holds both levels issues both levels' code for every block of either.
+// Returns whether the ray moved.
+// The march's end: ex (skip_box's exits) of the first event whose voxel it could not prove empty.  Returns false when
+// nothing beyond the current voxel is proven (its own row is at or below its block's ceiling).
+template <bool STATS>
+__device__ __forceinline__ bool ceil_march(const CastParams& P, const uint32_t* __restrict__ ceilp, const int16_t* __restrict__ ceilf,
+                                           const Ray& R, uint32_t wm, int32_t ex[3], Stats& st) {
+    const uint32_t lsh = P.ceil_sh[0];  // the finest level's blocks: 2^lsh columns
+    const uint32_t bm = (1u << lsh) - 1u, rows = (wm + 1u) >> lsh;
+    const int32_t wy = (int32_t)((uint32_t)R.r[1] & wm);
+    const uint32_t wx = (uint32_t)R.r[0] & wm, wz = (uint32_t)R.r[2] & wm;
+    // per axis the next block-boundary event: its index from the current state (the cells left in the block) and value
+    March m;
+    m.jx = (int32_t)(R.s[0] > 0 ? bm - (wx & bm) : (wx & bm));
+    m.jz = (int32_t)(R.s[2] > 0 ? bm - (wz & bm) : (wz & bm));
+    m.Ex = on_grid(R.T[0], m.jx, R.a(0));
+    m.Ez = on_grid(R.T[2], m.jz, R.a(2));
+    m.bx = wx >> lsh;
+    m.bz = wz >> lsh;
+    m.Ein = -__builtin_inf();
+    m.ein_axis = -1;
+    m.ein_j = 0;
+    march_level<STATS, false>(R, wy, lsh, rows, 1024, [&](uint32_t i) { return (int32_t)(int16_t)(ceilp[i] & 0xFFFFu); }, m, st);
+    const int32_t c_axis = m.stop_axis, c_j = m.stop_j;
+    if (ceilf && R.steps - march_reach(m, wy) >= kMarchFineSpan) {  // (ceilf: uniform)
+        // the 4-column block the entering event left the ray in (entered in z: the x events before it are those strictly
+        // below it; in x: the z events at or below it; the first block: none)
+        const bool ez = m.ein_axis == 2;
+        double F;
+        int32_t n = count_est(ez ? R.T[0] : R.T[2], ez ? R.a(0) : R.a(2), ez ? R.inv_a(0) : R.inv_a(2), m.Ein, (float)m.Ein, F);
+        n += (ez ? F < m.Ein : F <= m.Ein) ? 1 : 0;
+        const int32_t kx = m.ein_axis == 0 ? m.ein_j + 1 : (ez ? n : 0), kz = ez ? m.ein_j + 1 : (m.ein_axis == 0 ? n : 0);
+        const uint32_t lx = ((uint32_t)(m.jx - kx) >> 2) & 3u, lz = ((uint32_t)(m.jz - kz) >> 2) & 3u;  // sub-blocks left after it
+        m.jx -= (int32_t)(lx << 2);
+        m.jz -= (int32_t)(lz << 2);
+        m.Ex = on_grid(R.T[0], m.jx, R.a(0));
+        m.Ez = on_grid(R.T[2], m.jz, R.a(2));
+        m.bx = (m.bx << 2) + (R.s[0] > 0 ? 3u - lx : lx);
+        m.bz = (m.bz << 2) + (R.s[2] > 0 ? 3u - lz : lz);
+        if (STATS) st.march_descents++;
+        march_level<STATS, true>(R, wy, lsh - 2u, rows << 2, kMarchFineMax, [&](uint32_t i) { return (int32_t)ceilf[i]; }, m, st);
+        if (march_reach(m, wy) > R.steps) {  // its end may lie beyond the budget: the first phase's stands
+            m.stop_axis = c_axis;
+            m.stop_j = c_j;
+        }
+    }
     // (selects on values: a dynamically indexed register array would go through scratch)
-    ex[0] = stop_axis == 0 ? stop_j : R.steps;
-    ex[1] = stop_axis == 1 ? stop_j : R.steps;
-    ex[2] = stop_axis == 2 ? stop_j : R.steps;
-    return stop_axis >= 0;
+    ex[0] = m.stop_axis == 0 ? m.stop_j : R.steps;
+    ex[1] = m.stop_axis == 1 ? m.stop_j : R.steps;
+    ex[2] = m.stop_axis == 2 ? m.stop_j : R.steps;
+    return m.stop_axis >= 0;
 }

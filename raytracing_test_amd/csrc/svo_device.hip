@@ -25,7 +25,8 @@ void svo::tree_release_device(svo_tree* t) {
     if (t->d_ceil) (void)hipFree(t->d_ceil);
     if (t->d_ceilp) (void)hipFree(t->d_ceilp);
     if (t->d_ceilq) (void)hipFree(t->d_ceilq);
-    t->d_ceil = t->d_ceilp = t->d_ceilq = nullptr;
+    if (t->d_ceilf) (void)hipFree(t->d_ceilf);
+    t->d_ceil = t->d_ceilp = t->d_ceilq = t->d_ceilf = nullptr;
     for (auto& e : t->scheds)
         if (e.d_buf) (void)hipFree(e.d_buf);
     t->scheds.clear();
@@ -56,14 +57,17 @@ static int upload_ceilings(svo_tree* t) {
         t->ceil_host.clear();
         t->ceilp_host.clear();
         t->ceilq_host.clear();
+        t->ceil_fine_host.clear();
         n = -1;
     }
     t->ceil_dirty.clear();
+    // (the fine table's size follows from the levels, as the others': one test covers the four)
     if (n <= 0 || (int64_t)t->ceil_host.size() != t->ceil_dev_n) {
         if (t->d_ceil) (void)hipFree(t->d_ceil);
         if (t->d_ceilp) (void)hipFree(t->d_ceilp);
         if (t->d_ceilq) (void)hipFree(t->d_ceilq);
-        t->d_ceil = t->d_ceilp = t->d_ceilq = nullptr;
+        if (t->d_ceilf) (void)hipFree(t->d_ceilf);
+        t->d_ceil = t->d_ceilp = t->d_ceilq = t->d_ceilf = nullptr;
         t->ceil_dev_n = 0;
     }
     t->ceil_levels = 0;
@@ -74,8 +78,10 @@ static int upload_ceilings(svo_tree* t) {
         HIP_TRY(hipMalloc(&t->d_ceil, m * sizeof(int16_t)), SVO_ENOMEM);
         HIP_TRY(hipMalloc(&t->d_ceilp, m * sizeof(uint32_t)), SVO_ENOMEM);
         HIP_TRY(hipMalloc(&t->d_ceilq, t->ceilq_host.size() * sizeof(uint64_t)), SVO_ENOMEM);
+        HIP_TRY(hipMalloc(&t->d_ceilf, t->ceil_fine_host.size() * sizeof(int16_t)), SVO_ENOMEM);
         t->ceil_dev_n = (int64_t)m;
     }
+    HIP_TRY(hipMemcpy(t->d_ceilf, t->ceil_fine_host.data(), t->ceil_fine_host.size() * sizeof(int16_t), hipMemcpyHostToDevice), SVO_EDEVICE);
     HIP_TRY(hipMemcpy(t->d_ceil, t->ceil_host.data(), m * sizeof(int16_t), hipMemcpyHostToDevice), SVO_EDEVICE);
     HIP_TRY(hipMemcpy(t->d_ceilp, t->ceilp_host.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice), SVO_EDEVICE);
     HIP_TRY(hipMemcpy(t->d_ceilq, t->ceilq_host.data(), t->ceilq_host.size() * sizeof(uint64_t), hipMemcpyHostToDevice), SVO_EDEVICE);
@@ -107,6 +113,11 @@ int svo::sync_ceilings(svo_tree* t) {
             HIP_TRY(hipMemcpy(reinterpret_cast<uint64_t*>(t->d_ceilq) + lo, t->ceilq_host.data() + lo, cnt * sizeof(uint64_t),
                               hipMemcpyHostToDevice), SVO_EDEVICE);
         }
+    }
+    for (const auto& z : rows.level[0]) {
+        const CeilFineSpan f = ceil_fine_span(t, z);
+        HIP_TRY(hipMemcpy(reinterpret_cast<int16_t*>(t->d_ceilf) + f.first, t->ceil_fine_host.data() + f.first, f.count * sizeof(int16_t),
+                          hipMemcpyHostToDevice), SVO_EDEVICE);
     }
     for (int32_t j = 0; j < n; j++) {
         const int64_t w = (int64_t)1 << (2 * (t->levels - kCeilK0 - j));

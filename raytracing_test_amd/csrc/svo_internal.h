@@ -117,6 +117,12 @@ struct svo_tree {
     int64_t ceil_dev_n = 0;            // elements of the d_ceil / d_ceilp allocations
     std::vector<int16_t> ceil_host;    // the host copies of d_ceil / d_ceilp (svo_tree_sync updates them in place)
     std::vector<uint32_t> ceilp_host;
+    // the fine ceilings, one level below d_ceil's finest (the march before the loop descends onto them, svo_ceil_march.h):
+    // the highest stored voxel row (int16, -1: none) of every aligned block of 4^(kCeilK0 - 1) x 4^(kCeilK0 - 1) columns,
+    // row-major [z][x].  A table of its own (ceil_fine_host its host copy, kept by the same upload / sync as the others);
+    // present iff ceil_levels > 0
+    void* d_ceilf = nullptr;
+    std::vector<int16_t> ceil_fine_host;
     // column rectangles {x0, z0, x1, z1} (wrapped, half-open) whose ceilings svo_tree_update's edits may have changed
     std::vector<std::array<int64_t, 4>> ceil_dirty;
     // frame schedules (svo_cast.hip sched_attach): per (stream, launch kind) the block durations of the last frame of one
@@ -151,13 +157,18 @@ int32_t tree_top_y(const svo_tree* t);  // svo_tree.cpp
 // [z][x] at out[off[j] ..]; returns the number of levels.
 constexpr int32_t kCeilK0 = SVO_CEIL_K0, kCeilMax = 4;  // 16-, 64-, 256- and 1024-column blocks
 constexpr int32_t kCeilPairStep = SVO_CEIL_PAIR_STEP;    // the pair table: level j with level j + kCeilPairStep
-int32_t tree_ceilings(const svo_tree* t, std::vector<int16_t>& out, int64_t off[kCeilMax]);
+constexpr int32_t kCeilFineSh = 2 * (kCeilK0 - 1);       // log2 of a fine block's width (one level below level 0)
+int32_t tree_ceilings(const svo_tree* t, std::vector<int16_t>& out, int64_t off[kCeilMax], std::vector<int16_t>* fine = nullptr);
 // levels 1 .. nlev-1 re-derived over the blocks holding columns [x0, x1) x [z0, z1)
 void ceilings_coarsen(const svo_tree* t, std::vector<int16_t>& out, const int64_t off[kCeilMax], int32_t nlev, int64_t x0, int64_t z0,
                       int64_t x1, int64_t z1);
 // every level over the columns [x0, x1) x [z0, z1) recomputed from the tree (an edit's region: svo_tree_sync)
 void ceilings_update_rect(const svo_tree* t, std::vector<int16_t>& out, const int64_t off[kCeilMax], int32_t nlev, int64_t x0, int64_t z0,
-                          int64_t x1, int64_t z1);
+                          int64_t x1, int64_t z1, std::vector<int16_t>* fine = nullptr);
+// The fine ceilings (svo_tree.d_ceilf: blocks of 4^(kCeilK0 - 1) columns, row-major [z][x]) of the whole tree, empty when
+// the tree has no ceiling levels.  tree_ceilings and ceilings_update_rect keep them when handed `fine`: their one walk over
+// the tree (the rectangle) then fills the fine table, and level 0 is its 4 x 4 maxima.
+void tree_ceilings_fine(const svo_tree* t, std::vector<int16_t>& out);
 void tree_release_device(svo_tree* t);  // svo_device.hip
 // take over device arrays built on `device` (node_cap / mat_cap elements allocated, the host image
 // already equal to their first nodes.size() / mats.size() elements): svo_device.hip

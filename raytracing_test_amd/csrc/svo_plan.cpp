@@ -203,7 +203,7 @@ static void ceil_quads(svo_tree* t, int32_t n, int64_t x0, int64_t z0, int64_t x
 
 int32_t ceil_tables_build(svo_tree* t) {
     int64_t off[kCeilMax] = {0, 0, 0, 0}, zr[kCeilMax][2], qr[2];
-    const int32_t n = tree_ceilings(t, t->ceil_host, off);
+    const int32_t n = tree_ceilings(t, t->ceil_host, off, &t->ceil_fine_host);  // (the fine table: empty when n == 0)
     for (int j = 0; j < kCeilMax; j++) t->ceil_off[j] = t->ceilp_off[j] = off[j];
     t->ceilp_host.assign(t->ceil_host.size(), 0u);
     t->ceilq_host.clear();
@@ -229,9 +229,18 @@ static void merge_rows(std::vector<std::pair<int64_t, int64_t>>& v) {
 }
 
 void ceil_tables_update(svo_tree* t, int32_t n, const std::array<int64_t, 4>& r, int64_t zr[kCeilMax][2], int64_t qr[2]) {
-    ceilings_update_rect(t, t->ceil_host, t->ceil_off, n, r[0], r[1], r[2], r[3]);
+    ceilings_update_rect(t, t->ceil_host, t->ceil_off, n, r[0], r[1], r[2], r[3], &t->ceil_fine_host);
     ceil_pairs(t, n, r[0], r[1], r[2], r[3], zr);
     ceil_quads(t, n, r[0], r[1], r[2], r[3], qr);
+}
+
+bool ceil_fine_for(int32_t launch_levels, int32_t first_level) { return launch_levels > 0 && first_level == 0; }
+
+CeilFineSpan ceil_fine_span(const svo_tree* t, const std::pair<int64_t, int64_t>& level0_rows) {
+    const int64_t w = (int64_t)1 << (2 * t->levels - kCeilFineSh);  // fine blocks per row
+    const int64_t per = (int64_t)1 << (2 * kCeilK0 - kCeilFineSh);  // fine rows per level-0 row
+    const int64_t lo = std::min(level0_rows.first * per, w), hi = std::min(level0_rows.second * per, w);
+    return {lo * w, std::max<int64_t>(0, hi - lo) * w};
 }
 
 void ceil_tables_update_all(svo_tree* t, int32_t n, const std::vector<std::array<int64_t, 4>>& rects, CeilRows* rows) {
@@ -242,7 +251,7 @@ void ceil_tables_update_all(svo_tree* t, int32_t n, const std::vector<std::array
     std::vector<std::array<int64_t, 4>> spans;
     for (const auto& r : rects) {
         int64_t zr[kCeilMax][2];
-        ceilings_update_rect(t, t->ceil_host, t->ceil_off, n, r[0], r[1], r[2], r[3]);
+        ceilings_update_rect(t, t->ceil_host, t->ceil_off, n, r[0], r[1], r[2], r[3], &t->ceil_fine_host);
         ceil_pairs(t, n, r[0], r[1], r[2], r[3], zr);
         for (int32_t j = 0; j < n; j++) rows->level[j].push_back({zr[j][0], zr[j][1]});
         spans.push_back({r[0] >> csh, r[1] >> csh, (r[2] - 1) >> csh, (r[3] - 1) >> csh});

@@ -51,6 +51,16 @@ struct CeilRows {
     std::vector<std::pair<int64_t, int64_t>> level[kCeilMax], quads;
 };
 void ceil_tables_update_all(svo_tree* t, int32_t n, const std::vector<std::array<int64_t, 4>>& rects, CeilRows* rows);
+// The fine ceilings (svo_tree.ceil_fine_host) are kept by the same three calls.  Their rows rewritten lie within the level-0
+// rows reported (a rectangle is widened to level-0 blocks, the pairs' rows to their partner level's): the elements of the
+// fine table, first and count, that an interval [first, last) of level-0 rows covers.
+struct CeilFineSpan {
+    int64_t first, count;
+};
+// whether a launch whose first ceiling level is `first_level` of the table, with `launch_levels` levels in use, marches on
+// the fine ceilings: they lie one level below the table's finest, so only a launch that starts there descends onto them
+bool ceil_fine_for(int32_t launch_levels, int32_t first_level);
+CeilFineSpan ceil_fine_span(const svo_tree* t, const std::pair<int64_t, int64_t>& level0_rows);
 
 // the tree's rewritten records (svo_tree.dirty_nodes, sorted here) as runs [first, last] of consecutive indices
 std::vector<std::pair<uint32_t, uint32_t>> dirty_runs(std::vector<uint32_t>& dirty);

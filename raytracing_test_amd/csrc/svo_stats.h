@@ -21,6 +21,7 @@ struct Stats {
     uint32_t above_top;                            // iterations that start above the tree's highest stored row
     uint32_t bends;                                // reflections and refractions (shading)
     uint32_t tints, tint_iters;                    // refractive voxels passed; iterations that ended passing one
+    uint32_t march_fine, march_descents;           // the march before the loop: 4-column blocks passed; descents onto them
 };
 
 // true on one lane of the active lanes (wave-level counters)
@@ -72,4 +73,11 @@ enum : int32_t {
     S_TINTS,
     S_TINT_ITERS = 27,
 };
-static_assert(S_TINT_ITERS + 1 <= SVO_STATS_HEADER, "the counters' slots end before the per-block stamps");
+// The fine march's counters, after them: a list of their own (MARCH_STAT_NAMES in raytracing_test_amd/__init__.py, in the
+// same order), so that the list above and STAT_NAMES stay the 28 slots every earlier reader of the buffer indexes.
+enum : int32_t {
+    S_MARCH_FINE = 28,
+    S_MARCH_DESCENTS,
+};
+static_assert(S_MARCH_FINE == S_TINT_ITERS + 1 && S_MARCH_DESCENTS + 1 <= SVO_STATS_HEADER,
+              "the counters' slots end before the per-block stamps");

@@ -206,7 +206,7 @@ __device__ __forceinline__ Hit trace(const CastParams& P, const Mem& mem, const 
     constexpr bool MARCH = CEIL == T_CEIL_PAIRS || CEIL == T_CEIL_QUADS;
     if (XS != T_XS_RESUME && MARCH && ceil_on && !done && (SEG ? lin : fast) && R.s[1] < 0 && R.steps > 0) {
         int32_t ex[3];
-        if (ceil_march<STATS>(P, ceilp, R, wm, ex, st)) (void)skip_box<TRACK, RB>(R, ex, wseg);
+        if (ceil_march<STATS>(P, ceilp, P.ceilf, R, wm, ex, st)) (void)skip_box<TRACK, RB>(R, ex, wseg);
     }
     while (!done) {
         // the voxel just entered is untested
@@ -569,6 +569,8 @@ __device__ __forceinline__ Hit trace(const CastParams& P, const Mem& mem, const 
         atomicAdd(P.stats + S_BENDS, (unsigned long long)st.bends);
         atomicAdd(P.stats + S_TINTS, (unsigned long long)st.tints);
         atomicAdd(P.stats + S_TINT_ITERS, (unsigned long long)st.tint_iters);
+        atomicAdd(P.stats + S_MARCH_FINE, (unsigned long long)st.march_fine);
+        atomicAdd(P.stats + S_MARCH_DESCENTS, (unsigned long long)st.march_descents);
         // per-ray work (offline analysis, bench.py SVO_RAY_WORK): 16-bit fields, lookups | iterations | brick steps | node loads
         if (ray_work)
             *ray_work = (unsigned long long)min(st.lookups, 65535u) | ((unsigned long long)min(st.iters, 65535u) << 16) |

@@ -184,8 +184,54 @@ struct CeilWalk {
 };
 }  // namespace
 
-int32_t svo::tree_ceilings(const svo_tree* t, std::vector<int16_t>& out, int64_t off[kCeilMax]) {
+namespace {
+// the highest stored row over every block of 2^bsh columns (`rows` blocks per row of `top`, preset to -1), by one walk
+void walk_all(const svo_tree* t, int32_t bsh, int64_t rows, int16_t* top) {
+    CeilWalk cw{t, bsh, rows, top};
+    const Node& root = t->nodes[0];
+    if (node_kind(root.info) != K_INTERIOR) {
+        cw.walk(0, 0, 0, 0, 0);
+        return;
+    }
+    // the root's children by column (x, z slot): each thread walks the four children over one
+    // quarter x quarter of the columns, so the blocks it writes are its own
+    const int32_t cs = 1 << (2 * (t->levels - 1));
+    auto quadrant = [&, cs](uint32_t xz) {
+        CeilWalk w = cw;
+        for (uint32_t y = 0; y < 4; y++) {
+            const uint32_t sl = ((xz >> 2) << 4) | (y << 2) | (xz & 3u);
+            if (!((root.mask >> sl) & 1ull)) continue;
+            const uint32_t ci = packed_index(root, sl);
+            w.walk(ci, (int32_t)(xz & 3u) * cs, (int32_t)y * cs, (int32_t)(xz >> 2) * cs, 1);
+        }
+    };
+    std::vector<std::thread> th;
+    uint32_t started = 0;
+    try {
+        for (; started < 16; started++) th.emplace_back(quadrant, started);
+    } catch (const std::system_error&) {
+        // (no more threads: the quadrants not started are walked here)
+    }
+    for (uint32_t xz = started; xz < 16; xz++) quadrant(xz);
+    for (auto& x : th) x.join();
+}
+}  // namespace
+
+// level 0 of `out` over the level-0 blocks [bx0, bx1) x [bz0, bz1) as the 4 x 4 maxima of the fine table
+static void level0_from_fine(const svo_tree* t, const std::vector<int16_t>& fine, int16_t* top, int64_t bx0, int64_t bz0, int64_t bx1, int64_t bz1) {
+    const int64_t rows = (int64_t)1 << (2 * (t->levels - kCeilK0)), per = (int64_t)1 << (2 * kCeilK0 - kCeilFineSh), frows = rows * per;
+    for (int64_t bz = bz0; bz < bz1; bz++)
+        for (int64_t bx = bx0; bx < bx1; bx++) {
+            int16_t v = -1;
+            for (int64_t dz = 0; dz < per; dz++)
+                for (int64_t dx = 0; dx < per; dx++) v = std::max(v, fine[(size_t)((bz * per + dz) * frows + bx * per + dx)]);
+            top[bz * rows + bx] = v;
+        }
+}
+
+int32_t svo::tree_ceilings(const svo_tree* t, std::vector<int16_t>& out, int64_t off[kCeilMax], std::vector<int16_t>* fine) {
     out.clear();
+    if (fine) fine->clear();
     const int32_t nlev = std::min<int32_t>(kCeilMax, t->levels - kCeilK0);
     if (nlev <= 0 || t->nodes.empty()) return 0;
     int64_t total = 0;
@@ -195,35 +241,23 @@ int32_t svo::tree_ceilings(const svo_tree* t, std::vector<int16_t>& out, int64_t
         total += rows * rows;
     }
     out.assign((size_t)total, (int16_t)-1);
-    CeilWalk cw{t, 2 * kCeilK0, (int64_t)1 << (2 * (t->levels - kCeilK0)), out.data()};
-    const Node& root = t->nodes[0];
-    if (node_kind(root.info) != K_INTERIOR) {
-        cw.walk(0, 0, 0, 0, 0);
+    const int64_t rows0 = (int64_t)1 << (2 * (t->levels - kCeilK0));
+    if (fine) {  // one walk fills the fine table; level 0 is its 4 x 4 maxima
+        tree_ceilings_fine(t, *fine);
+        level0_from_fine(t, *fine, out.data(), 0, 0, rows0, rows0);
     } else {
-        // the root's children by column (x, z slot): each thread walks the four children over one
-        // quarter x quarter of the columns, so the blocks it writes are its own
-        const int32_t cs = 1 << (2 * (t->levels - 1));
-        auto quadrant = [&, cs](uint32_t xz) {
-            CeilWalk w = cw;
-            for (uint32_t y = 0; y < 4; y++) {
-                const uint32_t sl = ((xz >> 2) << 4) | (y << 2) | (xz & 3u);
-                if (!((root.mask >> sl) & 1ull)) continue;
-                const uint32_t ci = packed_index(root, sl);
-                w.walk(ci, (int32_t)(xz & 3u) * cs, (int32_t)y * cs, (int32_t)(xz >> 2) * cs, 1);
-            }
-        };
-        std::vector<std::thread> th;
-        uint32_t started = 0;
-        try {
-            for (; started < 16; started++) th.emplace_back(quadrant, started);
-        } catch (const std::system_error&) {
-            // (no more threads: the quadrants not started are walked here)
-        }
-        for (uint32_t xz = started; xz < 16; xz++) quadrant(xz);
-        for (auto& x : th) x.join();
+        walk_all(t, 2 * kCeilK0, rows0, out.data());
     }
     ceilings_coarsen(t, out, off, nlev, 0, 0, (int64_t)1 << (2 * t->levels), (int64_t)1 << (2 * t->levels));
     return nlev;
+}
+
+void svo::tree_ceilings_fine(const svo_tree* t, std::vector<int16_t>& out) {
+    out.clear();
+    if (t->levels - kCeilK0 <= 0 || t->nodes.empty()) return;
+    const int64_t rows = (int64_t)1 << (2 * t->levels - kCeilFineSh);
+    out.assign((size_t)(rows * rows), (int16_t)-1);
+    walk_all(t, kCeilFineSh, rows, out.data());
 }
 
 // levels 1 .. nlev-1 as 4 x 4 maxima of the finer level, over the blocks that hold columns [x0, x1) x [z0, z1)
@@ -281,20 +315,48 @@ struct CeilRectWalk {
 };
 }  // namespace
 
-void svo::ceilings_update_rect(const svo_tree* t, std::vector<int16_t>& out, const int64_t off[kCeilMax], int32_t nlev, int64_t x0,
-                               int64_t z0, int64_t x1, int64_t z1) {
-    if (nlev <= 0 || t->nodes.empty()) return;
+// (the table `top` of blocks of 2^bsh columns, `rows` per row, over a rectangle aligned to level-0 blocks)
+static void rect_rewalk(const svo_tree* t, int32_t bsh, int64_t rows, int16_t* top, int64_t x0, int64_t z0, int64_t x1, int64_t z1) {
+    for (int64_t bz = z0 >> bsh; bz < z1 >> bsh; bz++)
+        for (int64_t bx = x0 >> bsh; bx < x1 >> bsh; bx++) top[bz * rows + bx] = -1;
+    CeilRectWalk w{CeilWalk{t, bsh, rows, top}, x0, z0, x1, z1};
+    w.walk(0, 0, 0, 0, 0);
+}
+
+// a column rectangle widened to whole level-0 blocks
+static void widen_rect(int64_t& x0, int64_t& z0, int64_t& x1, int64_t& z1) {
     const int32_t bsh = 2 * kCeilK0;
-    const int64_t rows = (int64_t)1 << (2 * (t->levels - kCeilK0));
     x0 = (x0 >> bsh) << bsh;
     z0 = (z0 >> bsh) << bsh;
     x1 = (((x1 - 1) >> bsh) + 1) << bsh;
     z1 = (((z1 - 1) >> bsh) + 1) << bsh;
-    for (int64_t bz = z0 >> bsh; bz < z1 >> bsh; bz++)
-        for (int64_t bx = x0 >> bsh; bx < x1 >> bsh; bx++) out[off[0] + bz * rows + bx] = -1;
-    CeilRectWalk w{CeilWalk{t, bsh, rows, out.data() + off[0]}, x0, z0, x1, z1};
-    w.walk(0, 0, 0, 0, 0);
+}
+
+void svo::ceilings_update_rect(const svo_tree* t, std::vector<int16_t>& out, const int64_t off[kCeilMax], int32_t nlev, int64_t x0,
+                               int64_t z0, int64_t x1, int64_t z1, std::vector<int16_t>* fine) {
+    if (nlev <= 0 || t->nodes.empty()) return;
+    widen_rect(x0, z0, x1, z1);
+    const int32_t bsh = 2 * kCeilK0;
+    if (fine && !fine->empty()) {  // one restricted walk, into the fine table; level 0 follows from it
+        rect_rewalk(t, kCeilFineSh, (int64_t)1 << (2 * t->levels - kCeilFineSh), fine->data(), x0, z0, x1, z1);
+        level0_from_fine(t, *fine, out.data() + off[0], x0 >> bsh, z0 >> bsh, x1 >> bsh, z1 >> bsh);
+    } else {
+        rect_rewalk(t, bsh, (int64_t)1 << (2 * (t->levels - kCeilK0)), out.data() + off[0], x0, z0, x1, z1);
+    }
     ceilings_coarsen(t, out, off, nlev, x0, z0, x1, z1);
+}
+
+extern "C" int svo_tree_ceilings_fine(const svo_tree* t, int16_t* out, int64_t cap, int32_t* shift, int64_t* n) {
+    if (!t || !shift || !n) SVO_FAIL(SVO_EINVAL, "svo_tree_ceilings_fine: NULL argument");
+    std::vector<int16_t> c;
+    tree_ceilings_fine(t, c);
+    *shift = kCeilFineSh;
+    *n = (int64_t)c.size();
+    if (out) {
+        if (cap < *n) SVO_FAIL(SVO_ERANGE, "svo_tree_ceilings_fine: buffer too small");
+        if (!c.empty()) memcpy(out, c.data(), c.size() * sizeof(int16_t));
+    }
+    return SVO_OK;
 }
 
 extern "C" int svo_tree_ceilings(const svo_tree* t, int16_t* out, int64_t cap, int32_t* levels, int64_t* n) {

@@ -130,6 +130,14 @@ inline int scan(const uint32_t* in, uint64_t* out, int64_t n, uint64_t* total, s
     return SVO_OK;
 }
 
+// the scans' temporaries of one call (`v` is scan's tmp_pool), freed on every exit of it
+struct ScanTmp {
+    std::vector<void*> v;
+    ~ScanTmp() {
+        for (void* x : v) (void)hipFree(x);
+    }
+};
+
 // device allocations of one build, freed on every exit
 struct Pool {
     std::vector<void*> p;

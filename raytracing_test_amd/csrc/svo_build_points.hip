@@ -122,19 +122,13 @@ int build_levels(const svo_points_desc* p, const uint32_t* in_view, Pool& pool, 
     uint32_t* flag;
     rc = pool.alloc(&flag, (size_t)n);
     if (rc) return rc;
-    std::vector<void*> scan_tmp;
-    struct FreeTmp {
-        std::vector<void*>& v;
-        ~FreeTmp() {
-            for (void* x : v) (void)hipFree(x);
-        }
-    } free_tmp{scan_tmp};
+    ScanTmp scan_tmp;
 
     // level 0: the stored voxels
     hipLaunchKernelGGL(k_point_winners, lanes(n), dim3(256), 0, nullptr, keys, vals, n, in_view, flag);
     HIP_TRY(hipGetLastError(), SVO_EDEVICE);
     uint64_t n0 = 0;
-    rc = scan(flag, off, n, &n0, scan_tmp);
+    rc = scan(flag, off, n, &n0, scan_tmp.v);
     if (rc) return rc;
     if (n0 == 0) {
         HIP_TRY(hipDeviceSynchronize(), SVO_EDEVICE);
@@ -157,7 +151,7 @@ int build_levels(const svo_points_desc* p, const uint32_t* in_view, Pool& pool, 
         hipLaunchKernelGGL(k_cell_heads, lanes(nc), dim3(256), 0, nullptr, S.key[k - 1], nc, flag);
         HIP_TRY(hipGetLastError(), SVO_EDEVICE);
         uint64_t np = 0;
-        rc = scan(flag, off, nc, &np, scan_tmp);
+        rc = scan(flag, off, nc, &np, scan_tmp.v);
         if (rc) return rc;
         uint64_t* pk;
         uint32_t* ps;

@@ -136,13 +136,7 @@ int compact(svo_tree* t, std::chrono::steady_clock::time_point clock0, std::chro
     const char* who = "svo_tree_compact_gpu";
     const int32_t L = t->levels;
     Pool pool;
-    std::vector<void*> tmp;
-    struct TmpFree {
-        std::vector<void*>& v;
-        ~TmpFree() {
-            for (void* x : v) (void)hipFree(x);
-        }
-    } tmp_free{tmp};
+    ScanTmp tmp;
     DevTree T;
     memset(&T, 0, sizeof(T));
     T.nodes = reinterpret_cast<const Node*>(t->d_nodes);
@@ -169,7 +163,7 @@ int compact(svo_tree* t, std::chrono::steady_clock::time_point clock0, std::chro
             hipLaunchKernelGGL(k_reach_count, dim3(blocks_for(std::min(kItemChunk, n - i0), 256)), dim3(256), 0, nullptr, cur, i0, n, cnt);
             HIP_TRY(hipGetLastError(), SVO_EDEVICE);
         }
-        rc = scan(cnt, off, n, &total, tmp);
+        rc = scan(cnt, off, n, &total, tmp.v);
         if (rc) return rc;
         if (total > t->synced_nodes) SVO_FAIL(SVO_ESTATE, std::string(who) + ": the tree's records do not form a tree");
         if (total == 0) break;

@@ -1,22 +1,39 @@
-// svo_patch_cells.h — the descent the cell-asking patches share (svo_patch_shapes.hip: boxes and balls; svo_patch_tree.hip:
-// a box of another tree).  Both change a resident tree by asking, per aligned cell, how the cell stands to the patch
-// (OUT / IN(id) / CUT: svo_shape_cell.h's numbers) and, per voxel of a cut brick, whether the patch decides it:
+// svo_patch_cells.h — the one descent by which every patch changes a resident tree on the device (svo_patch_volume.hip:
+// a dense box; svo_patch_points.hip: a sparse list of edits; svo_patch_shapes.hip: boxes and balls; svo_patch_tree.hip: a
+// box of another tree).  Level-synchronous from the anchor: one wavefront per item (a region that is re-emitted), lane =
+// child slot (voxel at the brick level), ballots for the masks, exclusive scans (hipCUB) for child-block and material-run
+// offsets, a count pass and a write pass per level, then a brick pass (k_brick_count / k_brick_write's rules over the
+// composite voxels), all into scratch; commit_cells puts the result into the tree (svo_patch_commit.h).  A child slot
+// becomes nothing, a K_SOLID record, the old record copied (it keeps its subtree), or an item of the next level: a new
+// child block at the tail.  Re-emitted interior regions are not re-collapsed, and a brick that would store no voxel
+// clears its slot bit instead, so no K_BRICK record with mask 0 exists.
+// The patch is a class P, passed to the kernels by value:
+//   P.nodes, P.nbase    the resident tree's records (read only: the patch is written to scratch); scratch record s >= 1
+//                       becomes node nbase + s - 1 of the tree
+//   P::Item             an item of a level's list: `node`, the place of its record among the scratch records (0 is the
+//                       anchor's), and `old`, `kind`, what the tree held there (svo_plan.h P_NODE / P_UNIFORM / P_EMPTY:
+//                       a node index or a material); then whatever else the patch's own functions need
+//   child_of(P, it, on, sl, cs, k)   what slot sl of item `it` becomes (children cs = 4^k voxels wide, k >= 1; on: the old
+//                       record of a P_NODE item): a struct with `what` (CH_*) and `a`, plus what next_item needs
+//   next_item(P, it, c, sl, cs, node)   the next level's item of a CH_NEXT child c, its record at scratch index `node`
+//   brick_voxel(P, it, v)            the composite voxel v (z<<4 | y<<2 | x) of a brick item
+//   superseded(P, it, on, c, sl)     optional, called by every lane of the count pass: the patch counts there what it
+//                       supersedes (the patches that do not define it count on the host)
+// and descend_cells takes the first item (the anchor's) from the caller.
+// The cell-asking patches (all but the points patch) share one Item (coordinates), one child_of, next_item and
+// brick_voxel, written here over two questions:
+//   P.relation(x, y, z, cs, k, &id)   the cell of cs = 4^k voxels (k >= 1) against the patch: svo_shape_cell.h's numbers
+//   P.voxel(x, y, z, &id)             true when the patch decides the voxel, *id then what it stores
+//   P.mats, P.levels                  with P.nodes what old_voxel reads (svo_tree_descent.h) where the patch does not decide
+//   P::kFull                          whether relation() ever answers SHAPE_FULL
 //   * an OUT cell keeps its record and its subtree (below a K_SOLID region: a synthesised K_SOLID, below an empty one
 //     nothing);
 //   * an IN cell is one K_SOLID record of the id at whatever level it sits, or a clear slot bit for id 0: nothing is read
 //     for it;
-//   * a CUT cell is re-emitted one level down: a new child block at the tail.  A cut brick is classified from its 64
-//     composite voxels (the patch's, else the old tree's: svo_tree_descent.h) by k_brick_count / k_brick_write's rules;
-//     one that stores no voxel clears its slot bit, so no K_BRICK record with mask 0 exists.  Cut interior cells are not
-//     re-collapsed.
-// Level-synchronous: one wavefront per cut cell, lane = child slot (voxel at the brick level), ballots for the masks,
-// exclusive scans (hipCUB) for child-block and material-run offsets, a count pass and a write pass per level.  An item
-// carries only what the tree held (svo_plan.h P_NODE / P_UNIFORM / P_EMPTY): every child asks the patch anew.
-// The patch is a class P, passed to the kernels by value:
-//   P.nodes, P.mats, P.levels   the resident tree (read only: the patch is written to scratch)
-//   P.nbase                     scratch record s >= 1 becomes node nbase + s - 1 of the tree
-//   P.relation(x, y, z, cs, k, &id)   the cell of cs = 4^k voxels (k >= 1) against the patch
-//   P.voxel(x, y, z, &id)             true when the patch decides the voxel, *id then what it stores
+//   * a CUT cell is re-emitted one level down, carrying only what the tree held: every child asks the patch anew.  A cut
+//     brick is classified from its 64 composite voxels (the patch's, else the old tree's);
+//   * a FULL cell is re-emitted one level down as though the tree held nothing there (P_EMPTY): the patch decides every
+//     voxel of it, so nothing of the old tree is read for it or below it, and a FULL brick stores a voxel.
 // Every node and material index is widened to 64 bits before it addresses memory.
 #pragma once
 
@@ -37,11 +54,25 @@
 
 namespace {
 
-// a cut cell of one level's list: where its record goes (Region.node: an index into the scratch records; 0 is the
-// anchor's), and what the tree held there (svo_plan.h P_NODE / P_UNIFORM / P_EMPTY: `old` is a node index or a material)
+// what a child slot of an item becomes
+enum : uint32_t { CH_NONE = 0u, CH_SOLID = 1u, CH_COPY = 2u, CH_NEXT = 3u };
+
+// the old record of an item (nothing is read for one that holds none)
+template <class P>
+__device__ __forceinline__ Node old_record(const P& T, const typename P::Item& it) {
+    return it.kind == P_NODE ? T.nodes[(uint64_t)it.old] : Node{0ull, 0u, K_INTERIOR};
+}
+
+// the patches that count what they supersede on the host define no hook of their own
+template <class P, class C>
+__device__ __forceinline__ void superseded(const P&, const typename P::Item&, const Node&, const C&, uint32_t) {}
+
+// ---- the cell-asking patches' item and functions
+
+// a cut cell of one level's list: its first voxel, where its record goes and what the tree held there
 struct Item {
-    Region r;
-    uint32_t old, kind;
+    int32_t x0, y0, z0;
+    uint32_t node, old, kind;
 };
 
 // the composite: the patch's id where it decides the voxel, the old tree's elsewhere (svo_tree_descent.h)
@@ -51,21 +82,20 @@ __device__ __forceinline__ uint32_t comp_voxel(const P& T, int32_t x, int32_t y,
     return T.voxel(x, y, z, &id) ? id : old_voxel(T, (uint32_t)x, (uint32_t)y, (uint32_t)z);
 }
 
-// what a child slot of a cell becomes
-enum : uint32_t { CH_NONE = 0u, CH_SOLID = 1u, CH_COPY = 2u, CH_NEXT = 3u };
 struct Child {
     uint32_t what;
     uint32_t a;  // CH_SOLID: the material; CH_COPY: the old record's index; CH_NEXT: the next item's `old`
     uint32_t b;  // CH_NEXT: the next item's kind
 };
 
-// slot sl of item `it` (children cs = 4^k voxels wide); on = the old record of a P_NODE item
 template <class P>
 __device__ Child child_of(const P& T, const Item& it, const Node& on, uint32_t sl, int32_t cs, int k) {
-    const int32_t x = it.r.x0 + (int32_t)(sl & 3u) * cs, y = it.r.y0 + (int32_t)((sl >> 2) & 3u) * cs, z = it.r.z0 + (int32_t)(sl >> 4) * cs;
+    const int32_t x = it.x0 + (int32_t)(sl & 3u) * cs, y = it.y0 + (int32_t)((sl >> 2) & 3u) * cs, z = it.z0 + (int32_t)(sl >> 4) * cs;
     uint32_t id;
     const uint32_t rel = T.relation(x, y, z, cs, k, &id);
     if (rel == SHAPE_IN) return id ? Child{CH_SOLID, id, 0u} : Child{CH_NONE, 0u, 0u};
+    if constexpr (P::kFull)
+        if (rel == SHAPE_FULL) return Child{CH_NEXT, 0u, P_EMPTY};
     // what the child held
     uint32_t okind = it.kind, old = it.old;
     uint64_t om = it.kind == P_UNIFORM ? ~0ull : 0ull;  // (k == 1) the voxels the old child stored
@@ -98,57 +128,64 @@ __device__ Child child_of(const P& T, const Item& it, const Node& on, uint32_t s
 }
 
 template <class P>
-__device__ __forceinline__ Node old_record(const P& T, const Item& it) {
-    return it.kind == P_NODE ? T.nodes[(uint64_t)it.old] : Node{0ull, 0u, K_INTERIOR};
+__device__ __forceinline__ Item next_item(const P&, Item it, Child c, uint32_t sl, int32_t cs, uint32_t node) {
+    return Item{it.x0 + (int32_t)(sl & 3u) * cs, it.y0 + (int32_t)((sl >> 2) & 3u) * cs, it.z0 + (int32_t)(sl >> 4) * cs, node, c.a, c.b};
 }
+
+template <class P>
+__device__ __forceinline__ uint32_t brick_voxel(const P& T, const Item& it, uint32_t v) {
+    return comp_voxel(T, it.x0 + (int32_t)(v & 3u), it.y0 + (int32_t)((v >> 2) & 3u), it.z0 + (int32_t)(v >> 4));
+}
+
+// ---- the kernels, over any patch
 
 // one wavefront per item, lane = child slot: the children that exist and those that go on to the next level's list
 template <class P>
-__global__ void k_cells_count(P T, const Item* cur, int64_t r0, int64_t n, int32_t cs, int k, uint32_t* nkid, uint32_t* nnext) {
+__global__ void k_cells_count(P T, const typename P::Item* cur, int64_t r0, int64_t n, int32_t cs, int k, uint32_t* nkid, uint32_t* nnext) {
     const int64_t r = r0 + (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     const uint32_t sl = threadIdx.x & 63u;
     if (r >= n) return;  // whole waves exit together
-    const Item it = cur[r];
-    const Child c = child_of(T, it, old_record(T, it), sl, cs, k);
+    const typename P::Item it = cur[r];
+    const Node on = old_record(T, it);
+    const auto c = child_of(T, it, on, sl, cs, k);
     const uint64_t kid = __ballot(c.what != CH_NONE), nx = __ballot(c.what == CH_NEXT);
     if (sl == 0) {
         nkid[r] = (uint32_t)__popcll(kid);
         nnext[r] = (uint32_t)__popcll(nx);
     }
+    superseded(T, it, on, c, sl);
 }
 
 // second pass: the item's INTERIOR record, its SOLID and copied children, the next level's items.  base: the scratch
 // index of this level's first child record
 template <class P>
-__global__ void k_cells_write(P T, const Item* cur, int64_t r0, int64_t n, int32_t cs, int k, const uint64_t* koff, const uint64_t* noff,
-                              uint64_t base, Node* out, Item* next) {
+__global__ void k_cells_write(P T, const typename P::Item* cur, int64_t r0, int64_t n, int32_t cs, int k, const uint64_t* koff,
+                              const uint64_t* noff, uint64_t base, Node* out, typename P::Item* next) {
     const int64_t r = r0 + (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     const uint32_t sl = threadIdx.x & 63u;
     if (r >= n) return;
-    const Item it = cur[r];
-    const Child c = child_of(T, it, old_record(T, it), sl, cs, k);
+    const typename P::Item it = cur[r];
+    const auto c = child_of(T, it, old_record(T, it), sl, cs, k);
     const uint64_t kid = __ballot(c.what != CH_NONE), nx = __ballot(c.what == CH_NEXT);
     const uint64_t below = (1ull << sl) - 1ull;
     const uint64_t kpos = base + koff[r] + (uint64_t)__popcll(kid & below);
     if (c.what == CH_NEXT) {
-        const Region R{it.r.x0 + (int32_t)(sl & 3u) * cs, it.r.y0 + (int32_t)((sl >> 2) & 3u) * cs, it.r.z0 + (int32_t)(sl >> 4) * cs, (uint32_t)kpos};
-        next[noff[r] + (uint64_t)__popcll(nx & below)] = Item{R, c.a, c.b};
+        next[noff[r] + (uint64_t)__popcll(nx & below)] = next_item(T, it, c, sl, cs, (uint32_t)kpos);
     } else if (c.what == CH_SOLID) {
         out[kpos] = Node{~0ull, 0u, K_SOLID | (c.a << 16)};
     } else if (c.what == CH_COPY) {
         out[kpos] = T.nodes[(uint64_t)c.a];
     }
-    if (sl == 0) out[it.r.node] = Node{kid, (uint32_t)(T.nbase + base + koff[r] - 1ull), K_INTERIOR};
+    if (sl == 0) out[it.node] = Node{kid, (uint32_t)(T.nbase + base + koff[r] - 1ull), K_INTERIOR};
 }
 
 // bricks, by k_brick_count / k_brick_write's rules over the composite voxels (every item stores at least one)
 template <class P>
-__global__ void k_cells_brick_count(P T, const Item* cur, int64_t r0, int64_t n, uint32_t* nmat) {
+__global__ void k_cells_brick_count(P T, const typename P::Item* cur, int64_t r0, int64_t n, uint32_t* nmat) {
     const int64_t r = r0 + (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     const uint32_t v = threadIdx.x & 63u;
     if (r >= n) return;
-    const Region R = cur[r].r;
-    const uint32_t c = comp_voxel(T, R.x0 + (int32_t)(v & 3u), R.y0 + (int32_t)((v >> 2) & 3u), R.z0 + (int32_t)(v >> 4));
+    const uint32_t c = brick_voxel(T, cur[r], v);
     const uint64_t solid = __ballot(c != G_EMPTY);
     const bool uni = g_uniform(c, solid);
     if (v == 0) nmat[r] = uni ? 0u : (uint32_t)__popcll(solid);
@@ -156,18 +193,18 @@ __global__ void k_cells_brick_count(P T, const Item* cur, int64_t r0, int64_t n,
 
 // mbase: the tree's material index of mats[0]
 template <class P>
-__global__ void k_cells_brick_write(P T, const Item* cur, int64_t r0, int64_t n, const uint64_t* moff, uint64_t mbase, Node* out,
+__global__ void k_cells_brick_write(P T, const typename P::Item* cur, int64_t r0, int64_t n, const uint64_t* moff, uint64_t mbase, Node* out,
                                     uint16_t* mats) {
     const int64_t r = r0 + (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     const uint32_t v = threadIdx.x & 63u;
     if (r >= n) return;
-    const Region R = cur[r].r;
-    const uint32_t c = comp_voxel(T, R.x0 + (int32_t)(v & 3u), R.y0 + (int32_t)((v >> 2) & 3u), R.z0 + (int32_t)(v >> 4));
+    const typename P::Item it = cur[r];
+    const uint32_t c = brick_voxel(T, it, v);
     const uint64_t solid = __ballot(c != G_EMPTY);
     const bool uni = g_uniform(c, solid);
     const uint32_t first = (uint32_t)__shfl((int)c, (int)__builtin_ctzll(solid | (1ull << 63)));
     if (!uni && c != G_EMPTY) mats[moff[r] + (uint64_t)__popcll(solid & ((1ull << v) - 1ull))] = (uint16_t)c;
-    if (v == 0) out[R.node] = uni ? Node{solid, 0u, K_BRICK | K_UNIFORM | (first << 16)} : Node{solid, (uint32_t)(mbase + moff[r]), K_BRICK};
+    if (v == 0) out[it.node] = uni ? Node{solid, 0u, K_BRICK | K_UNIFORM | (first << 16)} : Node{solid, (uint32_t)(mbase + moff[r]), K_BRICK};
 }
 
 // A finished descent in scratch (pool's): out[0] the anchor's new record, out[1 .. used) the node tail, mats[0 .. n_mats)
@@ -179,13 +216,17 @@ struct CellsTail {
     uint64_t n_mats = 0;
 };
 
-// The level loop, from the anchor down to the bricks.  lone_root: the whole extent is one uniform region, and the root is
-// this record without children (nothing descends).  mbase: the tree's material index of the tail's first entry.  tmp holds
-// the scans' temporaries, which the caller frees after the device has finished.
+// the anchor as the cell-asking patches' first item
+inline Item anchor_item(const PatchAnchor& a) { return Item{a.o[0], a.o[1], a.o[2], 0u, a.old, a.kind}; }
+
+// The level loop, from the anchor down to the bricks of a tree L levels deep.  first: the anchor's item (node 0), at
+// `depth`.  lone_root: the whole extent is one uniform region, and the root is this record without children (nothing
+// descends).  mbase: the tree's material index of the tail's first entry.  tmp holds the scans' temporaries, which the
+// caller frees after the device has finished.
 template <class P>
-int descend_cells(const P& T, const char* who, const PatchAnchor& anchor, const Node* lone_root, uint64_t mbase, Pool& pool,
-                  std::vector<void*>& tmp, CellsTail* tail) {
-    const int32_t L = T.levels;
+int descend_cells(const P& T, const char* who, int32_t L, int32_t depth, const typename P::Item& first, const Node* lone_root, uint64_t mbase,
+                  Pool& pool, std::vector<void*>& tmp, CellsTail* tail) {
+    using Item = typename P::Item;
     // scratch records: [0] the anchor's, [1 ..) the appended tail; grown per level (capacity doubling, device copies)
     uint64_t cap = 1 << 12, used = 1, n_mats = 0;
     Node* out;
@@ -207,7 +248,6 @@ int descend_cells(const P& T, const char* who, const PatchAnchor& anchor, const 
     };
     uint16_t* mats = nullptr;
 
-    const Item first{Region{anchor.o[0], anchor.o[1], anchor.o[2], 0u}, anchor.old, anchor.kind};
     int64_t ncur = 1;
     if (lone_root) {
         HIP_TRY(hipMemcpy(out, lone_root, sizeof(Node), hipMemcpyHostToDevice), SVO_EDEVICE);
@@ -217,7 +257,7 @@ int descend_cells(const P& T, const char* who, const PatchAnchor& anchor, const 
     rc = pool.alloc(&cur, 1);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(cur, &first, sizeof(Item), hipMemcpyHostToDevice), SVO_EDEVICE);
-    for (int d = anchor.depth; d < L && ncur > 0; d++) {
+    for (int d = depth; d < L && ncur > 0; d++) {
         const int32_t cs = 1 << (2 * (L - d - 1));
         if (d == L - 1) {
             uint32_t* nmat;
@@ -274,7 +314,7 @@ int descend_cells(const P& T, const char* who, const PatchAnchor& anchor, const 
 }
 
 // The finished descent put into the tree (svo_patch_commit.h), with what follows a commit: the garbage counts (gnodes /
-// gmats superseded; a restart leaves none), the tree's top row, the ceilings over `rects` (room for them is reserved in
+// gmats superseded, counted by a host walk or by the patch's hook; a restart leaves none), the tree's top row, the ceilings over `rects` (room for them is reserved in
 // svo_tree.ceil_dirty by the caller) and svo_tree_patch_times' three figures (clock0: after the entry synchronisation;
 // clock1: after the descent).
 inline int commit_cells(svo_tree* t, const char* who, const CellsTail& tail, const PatchAnchor& anchor, uint64_t nbase, uint64_t mbase,

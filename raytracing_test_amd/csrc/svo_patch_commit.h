@@ -1,5 +1,5 @@
-// svo_patch_commit.h — how the device-side patches (svo_patch_volume.hip: a dense box; svo_patch_points.hip: a sparse list
-// of edits) put their result into a resident tree.  A patch is written to scratch first; once its totals are known the
+// svo_patch_commit.h — how the device-side patches put their result into a resident tree (commit_cells of
+// svo_patch_cells.h, the one descent of them all, calls it).  A patch is written to scratch first; once its totals are known the
 // device arrays are grown when the tail would not fit (emit_tree's slack rule), the tail is appended, the anchor's one
 // record is rewritten in place, and the tail and that record are copied back to the host image.
 #pragma once

@@ -7,8 +7,8 @@
 //     turned into 0, compacted to a sorted list of distinct keys;
 //   * anchor: the deepest interior record of the host image whose region holds every edit (svo_plan.cpp points_anchor),
 //     from the digits E's first and last key have in common: two 8-byte reads back;
-//   * descent: level-synchronous from the anchor, one wavefront per touched region, lane = child slot, as
-//     svo_patch_volume.hip's.  An item is a region with what it held (svo_plan.h P_NODE / P_UNIFORM / P_EMPTY), its range
+//   * descent: svo_patch_cells.h's, shared with the other patches (its kernels, level loop and commit), with this file's
+//     own item, child_of, next_item, brick_voxel and superseded hook.  An item is a region with what it held (svo_plan.h P_NODE / P_UNIFORM / P_EMPTY), its range
 //     [e0, e1) of E and the place of its new record.  A child is touched when E holds a key under it (a binary search on
 //     that level's digit inside the item's range).  An untouched child is the old record copied, a synthesised K_SOLID
 //     below a uniform region, or nothing; a touched one goes on to the next level's list, and at the brick level it is
@@ -16,10 +16,9 @@
 //     something — so no K_BRICK record with mask 0 exists;
 //   * bricks: k_brick_count / k_brick_write's rules, lane = voxel; the composite voxel is the edit where E has one, else
 //     the old brick's, read from the old record directly;
-//   * garbage is counted where the old records are read: the old child block of every P_NODE item, the material run of
-//     every touched old non-uniform brick (atomics on two scratch words);
-//   * commit: svo_patch_commit.h, shared with the volume patch — everything is in scratch and the ids are checked before
-//     the tree is touched;
+//   * garbage is counted where the old records are read, in the count pass: the old child block of every P_NODE item, the
+//     material run of every touched old non-uniform brick (atomics on two scratch words, read back after the descent);
+//   * commit: commit_cells — everything is in scratch and the ids are checked before the tree is touched;
 //   * ceilings: the distinct 16 x 16-column blocks E touches come back (8 B each), are merged into rectangles on the host
 //     (svo_plan.cpp ceil_block_rects) and recomputed exactly by sync_ceilings.
 // Scratch: 24 B per point for the sort, 4 + 8 B per point for the flags and offsets of the compaction, 10 B per edit for
@@ -40,8 +39,7 @@
 #include "svo_build_emit.h"
 #include "svo_hip.h"
 #include "svo_internal.h"
-#include "svo_patch_commit.h"
-#include "svo_plan.h"
+#include "svo_patch_cells.h"
 #include "svo_point_keys.h"
 
 using namespace svo;
@@ -93,10 +91,11 @@ __global__ void k_block_compact(const uint64_t* blocks, const uint32_t* head, co
 
 // a region of one level's list: its record's place among the scratch records (0 is the anchor's), what it held (svo_plan.h
 // P_*: `old` is a node index or a material), and its edits E[e0 .. e1) (n < 2^31)
-struct Item {
+struct EditItem {
     uint32_t node, old, kind, e0, e1;
 };
 
+// the patch as svo_patch_cells.h's kernels ask it
 struct DevEdits {
     const uint64_t* ekeys;  // E: distinct keys, ascending
     const uint16_t* evals;  // their resolved ids (0: erase)
@@ -104,6 +103,7 @@ struct DevEdits {
     const uint16_t* mats;
     uint64_t nbase;         // scratch record s >= 1 becomes node nbase + s - 1 of the tree
     unsigned long long* garbage;  // [0] node records, [1] material entries superseded
+    using Item = EditItem;
 };
 
 // the first entry of E[e0 .. e1) whose digit (key >> sh) & 63 is not below dg; the range shares every digit above
@@ -118,8 +118,7 @@ __device__ __forceinline__ uint32_t digit_lower(const uint64_t* ekeys, uint32_t 
 }
 
 // what a child slot of an item becomes
-enum : uint32_t { CH_NONE = 0u, CH_SOLID = 1u, CH_COPY = 2u, CH_NEXT = 3u };
-struct Child {
+struct EditChild {
     uint32_t what;
     uint32_t a;       // CH_SOLID: the material; CH_COPY: the old record's index; CH_NEXT: the next item's `old`
     uint32_t b;       // CH_NEXT: the next item's kind
@@ -128,7 +127,7 @@ struct Child {
 };
 
 // slot sl of item `it`, whose children are 4^k voxels wide (k >= 1; k == 1: bricks); on = the old record of a P_NODE item
-__device__ Child child_of(const DevEdits& P, const Item& it, const Node& on, uint32_t sl, int k) {
+__device__ EditChild child_of(const DevEdits& P, const EditItem& it, const Node& on, uint32_t sl, int32_t, int k) {
     const uint32_t c0 = digit_lower(P.ekeys, it.e0, it.e1, 6 * k, sl), c1 = digit_lower(P.ekeys, c0, it.e1, 6 * k, sl + 1u);
     const bool touched = c1 > c0;
     // what the child held
@@ -139,7 +138,7 @@ __device__ Child child_of(const DevEdits& P, const Item& it, const Node& on, uin
         okind = P_EMPTY;
         if ((on.mask >> sl) & 1ull) {
             old = on.ref + (uint32_t)__popcll(on.mask & ((1ull << sl) - 1ull));
-            if (!touched) return Child{CH_COPY, old, 0u, 0u, 0u, 0u};
+            if (!touched) return EditChild{CH_COPY, old, 0u, 0u, 0u, 0u};
             const Node oc = P.nodes[(uint64_t)old];
             okind = P_NODE;
             om = oc.mask;
@@ -152,7 +151,7 @@ __device__ Child child_of(const DevEdits& P, const Item& it, const Node& on, uin
             }
         }
     }
-    if (!touched) return okind == P_UNIFORM ? Child{CH_SOLID, old, 0u, 0u, 0u, 0u} : Child{CH_NONE, 0u, 0u, 0u, 0u, 0u};
+    if (!touched) return okind == P_UNIFORM ? EditChild{CH_SOLID, old, 0u, 0u, 0u, 0u} : EditChild{CH_NONE, 0u, 0u, 0u, 0u, 0u};
     if (k == 1) {  // a touched brick: absent unless a composite voxel is stored (at most 64 entries of E)
         uint64_t em = 0, en = 0;
         for (uint32_t e = c0; e < c1; e++) {
@@ -160,13 +159,13 @@ __device__ Child child_of(const DevEdits& P, const Item& it, const Node& on, uin
             em |= bit;
             if (P.evals[e] != 0) en |= bit;
         }
-        if (((om & ~em) | en) == 0ull) return Child{CH_NONE, 0u, 0u, 0u, 0u, gmats};
+        if (((om & ~em) | en) == 0ull) return EditChild{CH_NONE, 0u, 0u, 0u, 0u, gmats};
     }
-    return Child{CH_NEXT, old, okind, c0, c1, gmats};
+    return EditChild{CH_NEXT, old, okind, c0, c1, gmats};
 }
 
-__device__ __forceinline__ Node old_record(const DevEdits& P, const Item& it) {
-    return it.kind == P_NODE ? P.nodes[(uint64_t)it.old] : Node{0ull, 0u, K_INTERIOR};
+__device__ __forceinline__ EditItem next_item(const DevEdits&, EditItem, EditChild c, uint32_t, int32_t, uint32_t node) {
+    return EditItem{node, c.a, c.b, c.e0, c.e1};
 }
 
 // the sum of v over the wavefront's 64 lanes, in every lane
@@ -176,49 +175,18 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
     return v;
 }
 
-// one wavefront per item, lane = child slot: the children that exist and those that go on to the next level's list; the
-// records this item supersedes
-__global__ void k_edit_count(DevEdits P, const Item* cur, int64_t r0, int64_t n, int k, uint32_t* nkid, uint32_t* nnext) {
-    const int64_t r = r0 + (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    const uint32_t sl = threadIdx.x & 63u;
-    if (r >= n) return;  // whole waves exit together
-    const Item it = cur[r];
-    const Node on = old_record(P, it);
-    const Child c = child_of(P, it, on, sl, k);
-    const uint64_t kid = __ballot(c.what != CH_NONE), nx = __ballot(c.what == CH_NEXT);
+// the records an item supersedes, counted where the old records are read (the count pass): its old child block, and the
+// material runs of its touched old bricks
+__device__ __forceinline__ void superseded(const DevEdits& P, const EditItem& it, const Node& on, const EditChild& c, uint32_t sl) {
     const uint32_t gm = wave_sum(c.gmats);
     if (sl == 0) {
-        nkid[r] = (uint32_t)__popcll(kid);
-        nnext[r] = (uint32_t)__popcll(nx);
-        if (it.kind == P_NODE && on.mask) atomicAdd(P.garbage, (unsigned long long)__popcll(on.mask));  // its old child block
+        if (it.kind == P_NODE && on.mask) atomicAdd(P.garbage, (unsigned long long)__popcll(on.mask));
         if (gm) atomicAdd(P.garbage + 1, (unsigned long long)gm);
     }
 }
 
-// second pass: the item's INTERIOR record, its SOLID and copied children, the next level's items.  base: the scratch
-// index of this level's first child record
-__global__ void k_edit_write(DevEdits P, const Item* cur, int64_t r0, int64_t n, int k, const uint64_t* koff, const uint64_t* noff, uint64_t base,
-                             Node* out, Item* next) {
-    const int64_t r = r0 + (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    const uint32_t sl = threadIdx.x & 63u;
-    if (r >= n) return;
-    const Item it = cur[r];
-    const Child c = child_of(P, it, old_record(P, it), sl, k);
-    const uint64_t kid = __ballot(c.what != CH_NONE), nx = __ballot(c.what == CH_NEXT);
-    const uint64_t below = (1ull << sl) - 1ull;
-    const uint64_t kpos = base + koff[r] + (uint64_t)__popcll(kid & below);
-    if (c.what == CH_NEXT) {
-        next[noff[r] + (uint64_t)__popcll(nx & below)] = Item{(uint32_t)kpos, c.a, c.b, c.e0, c.e1};
-    } else if (c.what == CH_SOLID) {
-        out[kpos] = Node{~0ull, 0u, K_SOLID | (c.a << 16)};
-    } else if (c.what == CH_COPY) {
-        out[kpos] = P.nodes[(uint64_t)c.a];
-    }
-    if (sl == 0) out[it.node] = Node{kid, (uint32_t)(P.nbase + base + koff[r] - 1ull), K_INTERIOR};
-}
-
 // voxel v of a brick item: the edit when E has one, else what the brick held
-__device__ uint32_t comp_voxel(const DevEdits& P, const Item& it, uint32_t v) {
+__device__ uint32_t brick_voxel(const DevEdits& P, const EditItem& it, uint32_t v) {
     const uint32_t e = digit_lower(P.ekeys, it.e0, it.e1, 0, v);
     if (e < it.e1 && (uint32_t)(P.ekeys[e] & 63ull) == v) return P.evals[e];
     if (it.kind == P_UNIFORM) return it.old;
@@ -226,32 +194,6 @@ __device__ uint32_t comp_voxel(const DevEdits& P, const Item& it, uint32_t v) {
     const Node ob = P.nodes[(uint64_t)it.old];  // a K_BRICK record (a K_SOLID child came as P_UNIFORM)
     if (!((ob.mask >> v) & 1ull)) return G_EMPTY;
     return (ob.info & K_UNIFORM) ? node_material(ob.info) : P.mats[(uint64_t)ob.ref + (uint64_t)__popcll(ob.mask & ((1ull << v) - 1ull))];
-}
-
-// bricks, by k_brick_count / k_brick_write's rules over the composite voxels (every item stores at least one)
-__global__ void k_edit_brick_count(DevEdits P, const Item* cur, int64_t r0, int64_t n, uint32_t* nmat) {
-    const int64_t r = r0 + (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    const uint32_t v = threadIdx.x & 63u;
-    if (r >= n) return;
-    const uint32_t c = comp_voxel(P, cur[r], v);
-    const uint64_t solid = __ballot(c != G_EMPTY);
-    const bool uni = g_uniform(c, solid);
-    if (v == 0) nmat[r] = uni ? 0u : (uint32_t)__popcll(solid);
-}
-
-// mbase: the tree's material index of mats[0]
-__global__ void k_edit_brick_write(DevEdits P, const Item* cur, int64_t r0, int64_t n, const uint64_t* moff, uint64_t mbase, Node* out,
-                                   uint16_t* mats) {
-    const int64_t r = r0 + (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-    const uint32_t v = threadIdx.x & 63u;
-    if (r >= n) return;
-    const Item it = cur[r];
-    const uint32_t c = comp_voxel(P, it, v);
-    const uint64_t solid = __ballot(c != G_EMPTY);
-    const bool uni = g_uniform(c, solid);
-    const uint32_t first = (uint32_t)__shfl((int)c, (int)__builtin_ctzll(solid | (1ull << 63)));
-    if (!uni && c != G_EMPTY) mats[moff[r] + (uint64_t)__popcll(solid & ((1ull << v) - 1ull))] = (uint16_t)c;
-    if (v == 0) out[it.node] = uni ? Node{solid, 0u, K_BRICK | K_UNIFORM | (first << 16)} : Node{solid, (uint32_t)(mbase + moff[r]), K_BRICK};
 }
 
 }  // namespace
@@ -297,20 +239,14 @@ extern "C" int svo_tree_patch_points_gpu(svo_tree* t, const int32_t* xyz, const 
         SVO_FAIL(SVO_ERANGE, "svo_tree_patch_points_gpu: an id is not below the tree's palette size, and a coordinate is outside [0, 4^levels)");
     if (bad & kBadId) SVO_FAIL(SVO_ERANGE, "svo_tree_patch_points_gpu: an id is not below the tree's palette size");
     if (bad & kBadCoord) SVO_FAIL(SVO_ERANGE, "svo_tree_patch_points_gpu: a coordinate is outside [0, 4^levels)");
-    std::vector<void*> tmp;
-    struct TmpFree {
-        std::vector<void*>& v;
-        ~TmpFree() {
-            for (void* x : v) (void)hipFree(x);
-        }
-    } tmp_free{tmp};
+    ScanTmp tmp;
     uint32_t* flag;
     rc = pool.alloc(&flag, (size_t)n);
     if (rc) return rc;
     hipLaunchKernelGGL(k_edit_last, lanes(n), dim3(256), 0, nullptr, S.keys, n, flag);
     HIP_TRY(hipGetLastError(), SVO_EDEVICE);
     uint64_t ne = 0;
-    rc = scan(flag, S.spare, n, &ne, tmp);
+    rc = scan(flag, S.spare, n, &ne, tmp.v);
     if (rc) return rc;
     uint64_t* ekeys;
     uint16_t* evals;
@@ -339,7 +275,7 @@ extern "C" int svo_tree_patch_points_gpu(svo_tree* t, const int32_t* xyz, const 
         uint64_t* uniq = db.Alternate();
         hipLaunchKernelGGL(k_block_heads, lanes((int64_t)ne), dim3(256), 0, nullptr, sorted, (int64_t)ne, flag);
         HIP_TRY(hipGetLastError(), SVO_EDEVICE);
-        rc = scan(flag, S.spare, (int64_t)ne, &nblk, tmp);
+        rc = scan(flag, S.spare, (int64_t)ne, &nblk, tmp.v);
         if (rc) return rc;
         hipLaunchKernelGGL(k_block_compact, lanes((int64_t)ne), dim3(256), 0, nullptr, sorted, flag, S.spare, (int64_t)ne, uniq);
         HIP_TRY(hipGetLastError(), SVO_EDEVICE);
@@ -365,85 +301,11 @@ extern "C" int svo_tree_patch_points_gpu(svo_tree* t, const int32_t* xyz, const 
     HIP_TRY(hipMemset(dgarb, 0, 16), SVO_EDEVICE);
     const DevEdits P{ekeys, evals, reinterpret_cast<const Node*>(t->d_nodes), reinterpret_cast<const uint16_t*>(t->d_mats), nbase, dgarb};
 
-    // scratch records: [0] the anchor's, [1 ..) the appended tail; grown per level (capacity doubling, device copies)
-    uint64_t cap = 1 << 12, used = 1, n_mats = 0;
-    Node* out;
-    rc = pool.alloc(&out, cap);
+    CellsTail tail;
+    rc = descend_cells(P, who, L, anchor.depth, EditItem{0u, anchor.old, anchor.kind, 0u, (uint32_t)ne}, nullptr, mbase, pool, tmp.v, &tail);
     if (rc) return rc;
-    auto reserve = [&](uint64_t need) -> int {
-        if (need <= cap) return SVO_OK;
-        uint64_t nc = cap;
-        while (nc < need) nc *= 2;
-        Node* nn;
-        int r2 = pool.alloc(&nn, nc);
-        if (r2) return r2;
-        HIP_TRY(hipMemcpy(nn, out, used * sizeof(Node), hipMemcpyDeviceToDevice), SVO_EDEVICE);
-        pool.release(out);
-        (void)hipFree(out);
-        out = nn;
-        cap = nc;
-        return SVO_OK;
-    };
-    uint16_t* mats = nullptr;
-    const Item first{0u, anchor.old, anchor.kind, 0u, (uint32_t)ne};
-    int64_t ncur = 1;
-    Item* cur;
-    rc = pool.alloc(&cur, 1);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(cur, &first, sizeof(Item), hipMemcpyHostToDevice), SVO_EDEVICE);
-    for (int d = anchor.depth; d < L && ncur > 0; d++) {
-        if (d == L - 1) {
-            uint32_t* nmat;
-            uint64_t* moff;
-            rc = pool.alloc(&nmat, ncur);
-            if (!rc) rc = pool.alloc(&moff, ncur);
-            if (rc) return rc;
-            rc = for_region_chunks(ncur, [&](int64_t r0, dim3 g) {
-                hipLaunchKernelGGL(k_edit_brick_count, g, dim3(256), 0, nullptr, P, cur, r0, ncur, nmat);
-            });
-            if (rc) return rc;
-            rc = scan(nmat, moff, ncur, &n_mats, tmp);
-            if (rc) return rc;
-            if (mbase + n_mats > 0xFFFFFFFFull) SVO_FAIL(SVO_ERANGE, std::string(who) + ": tree exceeds 2^32 material entries");
-            rc = pool.alloc(&mats, n_mats + 1);
-            if (rc) return rc;
-            rc = for_region_chunks(ncur, [&](int64_t r0, dim3 g) {
-                hipLaunchKernelGGL(k_edit_brick_write, g, dim3(256), 0, nullptr, P, cur, r0, ncur, moff, mbase, out, mats);
-            });
-            if (rc) return rc;
-            break;
-        }
-        uint32_t *nkid, *nnext;
-        uint64_t *koff, *noff, nk = 0, nn = 0;
-        rc = pool.alloc(&nkid, ncur);
-        if (!rc) rc = pool.alloc(&nnext, ncur);
-        if (!rc) rc = pool.alloc(&koff, ncur);
-        if (!rc) rc = pool.alloc(&noff, ncur);
-        if (rc) return rc;
-        rc = for_region_chunks(ncur, [&](int64_t r0, dim3 g) {
-            hipLaunchKernelGGL(k_edit_count, g, dim3(256), 0, nullptr, P, cur, r0, ncur, L - d - 1, nkid, nnext);
-        });
-        if (rc) return rc;
-        rc = scan(nkid, koff, ncur, &nk, tmp);
-        if (!rc) rc = scan(nnext, noff, ncur, &nn, tmp);
-        if (rc) return rc;
-        if (nbase + used - 1 + nk > 0xFFFFFFFFull) SVO_FAIL(SVO_ERANGE, std::string(who) + ": tree exceeds 2^32 nodes");
-        rc = reserve(used + nk);
-        if (rc) return rc;
-        Item* next;
-        rc = pool.alloc(&next, nn);
-        if (rc) return rc;
-        rc = for_region_chunks(ncur, [&](int64_t r0, dim3 g) {
-            hipLaunchKernelGGL(k_edit_write, g, dim3(256), 0, nullptr, P, cur, r0, ncur, L - d - 1, koff, noff, used, out, next);
-        });
-        if (rc) return rc;
-        used += nk;
-        cur = next;
-        ncur = (int64_t)nn;
-    }
     unsigned long long garb[2] = {0, 0};
-    HIP_TRY(hipMemcpy(garb, dgarb, 16, hipMemcpyDeviceToHost), SVO_EDEVICE);  // (the null stream: every pass is over)
-    HIP_TRY(hipDeviceSynchronize(), SVO_EDEVICE);
+    HIP_TRY(hipMemcpy(garb, dgarb, 16, hipMemcpyDeviceToHost), SVO_EDEVICE);
     std::vector<std::array<int64_t, 4>> rects;
     try {
         rects = ceil_block_rects(hblocks);
@@ -453,24 +315,5 @@ extern "C" int svo_tree_patch_points_gpu(svo_tree* t, const int32_t* xyz, const 
     }
     const auto clock1 = std::chrono::steady_clock::now();
 
-    // the totals are known and nothing of the tree has changed yet: room, then the tail, then the anchor's record
-    rc = commit_patch(t, who, PatchTail{out, used - 1, mats, n_mats, anchor.node, nbase, mbase, false});
-    if (rc) return rc;
-    t->garbage_nodes += garb[0];
-    t->garbage_mats += garb[1];
-    const auto clock2 = std::chrono::steady_clock::now();
-    {
-        std::lock_guard<std::mutex> lock(t->top_mu);
-        t->top_valid = false;
-    }
-    t->dev_top_y = tree_top_y(t);
-    for (const auto& r : rects) t->ceil_dirty.push_back(r);
-    rc = sync_ceilings(t);
-    const auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double, std::milli>(b - a).count();
-    };
-    t->patch_ms[0] = ms(clock0, clock1);
-    t->patch_ms[1] = ms(clock1, clock2);
-    t->patch_ms[2] = ms(clock2, std::chrono::steady_clock::now());
-    return rc;
+    return commit_cells(t, who, tail, anchor, nbase, mbase, garb[0], garb[1], rects, clock0, clock1);
 }

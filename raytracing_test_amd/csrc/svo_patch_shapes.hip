@@ -1,8 +1,8 @@
 // svo_patch_shapes.hip — svo_tree_patch_shapes_gpu: a resident tree is changed, on the device, by an ordered list of solid
 // shapes (boxes and balls, each with the id it stores; id 0 erases).  A voxel ends up with the id of the last shape that
-// contains it; the cost follows the shapes' surfaces, never their volumes.  The descent is svo_patch_volume.hip's, with
-// the box's class pyramid replaced by a closed form (svo_shape_cell.h cell_relation, asked per cell over the whole table);
-// its kernels and level loop are svo_patch_cells.h's, shared with svo_patch_tree.hip: a cell no shape touches is OUT, a
+// contains it; the cost follows the shapes' surfaces, never their volumes.  The descent, its kernels, its level loop and
+// its commit are svo_patch_cells.h's, shared with the other patches; the question a cell asks is a closed form
+// (svo_shape_cell.h cell_relation, asked per cell over the whole table): a cell no shape touches is OUT, a
 // cell wholly inside the deciding shape IN, a cell the deciding shape cuts CUT.  The table sits in HBM and is indexed by
 // the loop counter alone, the same in every lane; it is not copied per lane.
 // The descent starts at the anchor the host finds on its image (svo_plan.cpp patch_anchor over the union of the shapes'
@@ -38,6 +38,8 @@ struct DevShapes {
     const uint16_t* mats;
     int32_t levels;
     uint64_t nbase;          // scratch record s >= 1 becomes node nbase + s - 1 of the tree
+    using Item = ::Item;
+    static constexpr bool kFull = false;
     __device__ uint32_t relation(int32_t x, int32_t y, int32_t z, int32_t cs, int, uint32_t* id) const {
         return cell_relation(shapes, n, x, y, z, cs, id);
     }
@@ -108,17 +110,11 @@ extern "C" int svo_tree_patch_shapes_gpu(svo_tree* t, const svo_shape* shapes, i
     HIP_TRY(hipMemcpy(dshapes, plan.table.data(), (size_t)ns * sizeof(ShapeRec), hipMemcpyHostToDevice), SVO_EDEVICE);
     const DevShapes P{dshapes, ns, reinterpret_cast<const Node*>(t->d_nodes), reinterpret_cast<const uint16_t*>(t->d_mats), L, nbase};
 
-    std::vector<void*> tmp;
-    struct TmpFree {
-        std::vector<void*>& v;
-        ~TmpFree() {
-            for (void* x : v) (void)hipFree(x);
-        }
-    } tmp_free{tmp};
+    ScanTmp tmp;
     // a root without children when the whole extent is IN
     const Node root = top_id == 0 ? Node{0ull, 0u, K_INTERIOR} : Node{~0ull, 0u, K_SOLID | (top_id << 16)};
     CellsTail tail;
-    rc = descend_cells(P, who, anchor, whole ? &root : nullptr, mbase, pool, tmp, &tail);
+    rc = descend_cells(P, who, L, anchor.depth, anchor_item(anchor), whole ? &root : nullptr, mbase, pool, tmp.v, &tail);
     if (rc) return rc;
     const auto clock1 = std::chrono::steady_clock::now();
 

@@ -1,8 +1,8 @@
 // svo_patch_tree.hip — svo_tree_patch_tree_gpu and svo_tree_patch_tree_oriented_gpu: a box of one resident tree (src) is
 // pasted into another (dst), on the device, at an offset that is on no grid — and, by the second call, turned or mirrored
 // by any of the 48 signed axis permutations, its ids through a table —, without expanding src's uniform regions: the cost
-// follows the box's surface and the src records reached in it, never the volume.  The descent, its kernels and its level
-// loop are svo_patch_cells.h's, shared with svo_patch_shapes.hip; the question a cell asks is svo_paste_cell.h's
+// follows the box's surface and the src records reached in it, never the volume.  The descent, its kernels, its level
+// loop and its commit are svo_patch_cells.h's, shared with the other patches; the question a cell asks is svo_paste_cell.h's
 // paste_relation: the aligned destination cell is clipped to the box, its ends are mapped into src (a shift; oriented: a
 // per-axis affine map, under which an aligned cs^3 box is still a cs^3 box), and it is compared with the at most
 // 2 x 2 x 2 aligned src cells it meets, each found by a walk from src's root (eight walks of at most 7 dependent loads
@@ -47,6 +47,8 @@ struct DevPasteOf {
     const uint16_t* mats;
     int32_t levels;
     uint64_t nbase;  // scratch record s >= 1 becomes node nbase + s - 1 of dst
+    using Item = ::Item;
+    static constexpr bool kFull = false;
     __device__ uint32_t relation(int32_t x, int32_t y, int32_t z, int32_t cs, int k, uint32_t* id) const {
         return relation_of(rec, src, x, y, z, cs, k, id);
     }
@@ -147,15 +149,9 @@ int paste_run(svo_tree* dst, const svo_tree* src, const char* who, const Rec& re
     rc = upload_id_map(pool, P.rec, src->palette.size());
     if (rc) return rc;
 
-    std::vector<void*> tmp;
-    struct TmpFree {
-        std::vector<void*>& v;
-        ~TmpFree() {
-            for (void* x : v) (void)hipFree(x);
-        }
-    } tmp_free{tmp};
+    ScanTmp tmp;
     CellsTail tail;
-    rc = descend_cells(P, who, anchor, nullptr, mbase, pool, tmp, &tail);
+    rc = descend_cells(P, who, L, anchor.depth, anchor_item(anchor), nullptr, mbase, pool, tmp.v, &tail);
     if (rc) return rc;
     const auto clock1 = std::chrono::steady_clock::now();
     return commit_cells(dst, who, tail, anchor, nbase, mbase, gnodes, gmats, rects, clock0, clock1);

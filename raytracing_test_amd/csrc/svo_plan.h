@@ -68,10 +68,9 @@ std::vector<std::pair<uint32_t, uint32_t>> dirty_runs(std::vector<uint32_t>& dir
 bool tree_unsynced(const svo_tree* t);
 
 // svo_tree_patch_volume_gpu (svo_patch_volume.hip) replaces the content of the box [lo, hi) of a resident tree.  What a
-// region held before the patch, as the patch's work items carry it:
+// region held before the patch, as the work items of every patch's descent carry it (svo_patch_cells.h):
 enum : uint32_t {
-    P_PLAIN = 0u,    // nothing: the region lies wholly inside the box and is emitted from the box alone
-    P_NODE = 1u,     // the record nodes[old] (INTERIOR above the brick level, BRICK at it)
+    P_NODE = 1u,    // the record nodes[old] (INTERIOR above the brick level, BRICK at it)
     P_UNIFORM = 2u,  // material `old` throughout (a K_SOLID record, or a region below one)
     P_EMPTY = 3u,    // nothing stored (a clear slot bit, or a region below one)
 };

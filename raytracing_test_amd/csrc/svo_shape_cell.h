@@ -29,7 +29,9 @@ struct ShapeRec {
 };
 static_assert(sizeof(ShapeRec) == 40, "the shape table is read as 40-byte records");
 
-enum : uint32_t { SHAPE_OUT = 0u, SHAPE_IN = 1u, SHAPE_CUT = 2u };
+// (SHAPE_FULL: the patch alone decides every voxel of the cell, and not uniformly.  No shape answers it: it is the volume
+// patch's, whose box holds arbitrary voxels, to svo_patch_cells.h)
+enum : uint32_t { SHAPE_OUT = 0u, SHAPE_IN = 1u, SHAPE_CUT = 2u, SHAPE_FULL = 3u };
 
 // The cell [x, x + cs) x [y, y + cs) x [z, z + cs) against one shape: OUT when no voxel of the cell lies in the shape, IN
 // when every voxel does, else CUT.  Box: the interval tests of the volume patch.  Ball: IN when the cell's farthest

@@ -1,5 +1,5 @@
 // svo_tree_descent.h — svo_tree_get_block's descent over a resident tree's arrays in HBM, for the kernels that re-emit
-// such a tree: the volume patch (svo_patch_volume.hip: the old content outside the box) and the compaction
+// such a tree: the patches (svo_patch_cells.h: the old content where the patch does not decide) and the compaction
 // (svo_compact.hip: the voxels of the old bricks), and for the lookup of scattered voxels (svo_build_points.hip:
 // svo_tree_get_blocks_gpu).  T holds the arrays and the depth: T.nodes, T.mats, T.levels.
 // Every node and material index is widened to 64 bits before it addresses memory.

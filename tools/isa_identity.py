@@ -1,10 +1,12 @@
 """Are the kernels of two builds the same instruction streams?
-usage: python tools/isa_identity.py [--max-name N] DIR_A DIR_B   (directories of `hipcc <build.py HIP_FLAGS> --offload-device-only -S` output, *.s)
+usage: python tools/isa_identity.py [--max-name N] [--alias OLD=NEW]... DIR_A DIR_B   (directories of `hipcc <build.py HIP_FLAGS> --offload-device-only -S` output, *.s)
 Each kernel is keyed by its demangled name without the `(anonymous namespace)::` qualifier; its text (label to end marker,
 comments dropped, local labels renamed by order of appearance) and its .amdhsa_ descriptor block are hashed together.
 Prints one line per kernel with the hash of each side and a final count; exits 1 unless both sides hold the same kernels
 with equal hashes.  --max-name N prints a name longer than N characters (hipCUB's template instances run to 2,800) as its
-first N characters, `...` and the hash of the whole name: the comparison is still by whole names."""
+first N characters, `...` and the hash of the whole name: the comparison is still by whole names.  --alias OLD=NEW is for a
+kernel that was renamed: DIR_A's kernel whose function name (the demangled name up to its parameter list, without `void `)
+is OLD is keyed under the name of DIR_B's kernel whose function name is NEW, and its line says so."""
 import glob
 import hashlib
 import os
@@ -61,16 +63,31 @@ def short(key, limit):
     return "%s...#%s" % (key[:limit], hashlib.sha256(key.encode()).hexdigest()[:12])
 
 
+def function_name(key):
+    return re.sub(r"^void ", "", key.split("(")[0])
+
+
 def main():
-    args, limit = sys.argv[1:], 0
-    if args and args[0] == "--max-name":
-        limit, args = int(args[1]), args[2:]
+    args, limit, aliases = sys.argv[1:], 0, []
+    while args and args[0] in ("--max-name", "--alias"):
+        if args[0] == "--max-name":
+            limit = int(args[1])
+        else:
+            aliases.append(args[1].split("=", 1))
+        args = args[2:]
     a, b = kernels(args[0]), kernels(args[1])
+    was = {}
+    for old, new in aliases:
+        (ka,), (kb,) = [k for k in a if function_name(k) == old], [k for k in b if function_name(k) == new]
+        assert kb not in a, kb
+        a[kb] = a.pop(ka)
+        was[kb] = old
     same = 0
     for key in sorted(set(a) | set(b)):
         ok = key in a and a[key] == b.get(key)
         same += ok
-        print("%-9s %-16s %-16s %s" % ("same" if ok else "DIFFERENT", digest(a.get(key)), digest(b.get(key)), short(key, limit)))
+        note = "   (was %s)" % was[key] if key in was else ""
+        print("%-9s %-16s %-16s %s%s" % ("same" if ok else "DIFFERENT", digest(a.get(key)), digest(b.get(key)), short(key, limit), note))
     name = [os.path.basename(os.path.normpath(d)) for d in args[:2]]
     print("%d kernels in %s, %d in %s, %d identical" % (len(a), name[0], len(b), name[1], same))
     return 0 if same == len(a) == len(b) else 1

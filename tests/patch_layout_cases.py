@@ -139,7 +139,9 @@ def cell_cases(rt):
 
 
 def sequence_cases(rt):
-    """(name, digest): a volume patch, a points patch, a shapes patch and a paste on one tree: tails behind tails"""
+    """(name, digest): a volume patch, a points patch, a shapes patch and a paste on one tree: tails behind tails.  This pins
+    the layout of four of the 49 ordered pairs of kinds; tests/test_gpu_mixed_ops.py checks the content, the garbage counts,
+    the host image and the ceilings of all of them, step by step, against a model (tests/mixed_ops_cases.py)."""
     old = old64()
     for view in VIEWS:
         src = _tree(rt, 3, _rand((64, 64, 64), 22), view)

@@ -52,9 +52,10 @@ STAT_NAMES = ("rays", "lookups", "node_loads", "skips", "skip_budget_out", "bric
               "wave_iters", "wave_brick_steps",
               "no_progress", "root_starts", "cache_empty", "wave_skips", "wave_descents",
               "path_starts", "ao_node_loads", "ceil_moves", "iters_above_top", "bends", "tints", "tint_iters")  # wave_*: per wave (64 rays)
-# the fine march's counters, in the slots after STAT_NAMES' (the second S_* enum of csrc/svo_stats.h): 4-column blocks the
-# march before the loop passed, and its descents from 16-column blocks onto them; cast_stats() returns them with the others
-MARCH_STAT_NAMES = ("march_fine", "march_descents")
+# the march's counters, in the slots after STAT_NAMES' (the second S_* enum of csrc/svo_stats.h): 4-column blocks the
+# march before the loop passed, its descents from 16-column blocks onto them, and the blocks it passed at its 64- and
+# 256-column levels; cast_stats() returns them with the others
+MARCH_STAT_NAMES = ("march_fine", "march_descents", "march_64", "march_256")
 STATS_HEADER = 32  # u64 counters before the per-block stamps (SVO_STATS_HEADER)
 MAX_FRAMES = 16  # SVO_MAX_FRAMES: frames in one launch
 WIRE_BYTES = 12  # SVO_WIRE_BYTES: the larger wire record (12 B general, 8 B compact: Tree.wire_bytes(desc))

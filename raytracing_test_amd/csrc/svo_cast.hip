@@ -173,6 +173,7 @@ static_assert(kCeilPrimary[1] - kCeilPrimary[0] == kCeilPairStep && kCeilShade[1
 static void set_ceilings(const svo_tree* t, const svo_cast_desc* d, CastParams& P, const int lv[2]) {
     P.ceil = nullptr;
     P.ceil_levels = 0;
+    P.march_n = 0;
     if (d->flags & SVO_CAST_NO_CEILINGS) return;
     P.ceil = reinterpret_cast<const int16_t*>(t->d_ceil);
     P.ceil_levels = t->ceil_levels > lv[1] ? 2 : (t->ceil_levels > lv[0] ? 1 : 0);
@@ -187,6 +188,13 @@ static void set_ceilings(const svo_tree* t, const svo_cast_desc* d, CastParams& 
         const int l = j < P.ceil_levels ? lv[j] : lv[0];
         P.ceil_sh[j] = 2u * (uint32_t)(kCeilK0 + l);
         P.ceil_off[j] = t->ceil_off[l];
+    }
+    // the coarser levels the march walks first (already in d_ceil: no table of their own)
+    const MarchParams mp = march_params(t, P.ceil_levels, lv[0]);
+    P.march_n = mp.n;
+    for (int j = 0; j < kMarchCoarseMax; j++) {
+        P.march_sh[j] = mp.sh[j];
+        P.march_off[j] = mp.off[j];
     }
 }
 

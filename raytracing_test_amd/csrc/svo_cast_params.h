@@ -87,6 +87,12 @@ struct CastParams {
     // the fine ceilings of the tree the rays walk (svo_tree.d_ceilf: 4-column blocks, row-major), which the march before
     // the loop descends onto (ceil_march); null: none, or the launch's first level is not the table's finest
     const int16_t* ceilf;
+    // the levels of `ceil` coarser than the launch's first that the march walks before it, coarsest first (march_levels,
+    // svo_plan.h): blocks 2^march_sh[j] columns wide, row-major at ceil + march_off[j]; each 4 times as wide as the next, the
+    // last 4 times as wide as the launch's first level.  march_n 0: the march starts on the first level's blocks
+    int32_t march_n;
+    uint32_t march_sh[2];
+    int64_t march_off[2];
     uint32_t* guard_trips;  // the tree's counter of progress-guard trips (svo_tree_guard_trips)
     // frame schedule (sched_attach): launch block b casts frame block sched_order[b] (null: b) and, with sched_cost,
     // writes its duration (100 MHz ticks) to sched_cost[frame block]

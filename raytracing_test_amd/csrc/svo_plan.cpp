@@ -236,6 +236,27 @@ void ceil_tables_update(svo_tree* t, int32_t n, const std::array<int64_t, 4>& r,
 
 bool ceil_fine_for(int32_t launch_levels, int32_t first_level) { return launch_levels > 0 && first_level == 0; }
 
+MarchLevels march_levels(int32_t ceil_levels, int32_t first_level, int32_t levels) {
+    MarchLevels m = {};
+    if (first_level < 0 || ceil_levels <= first_level) return m;
+    int32_t top = std::min(std::min(ceil_levels, (int32_t)kCeilMax) - 1, first_level + kMarchCoarseMax);
+    while (top > first_level && levels - kCeilK0 - top < 1) top--;  // (4^(levels - kCeilK0 - l) blocks per row: at least 4)
+    for (int32_t l = top; l > first_level; l--) m.level[m.n++] = l;
+    return m;
+}
+
+MarchParams march_params(const svo_tree* t, int32_t launch_levels, int32_t first_level) {
+    MarchParams p = {};
+    if (launch_levels <= 0) return p;
+    const MarchLevels ml = march_levels(t->ceil_levels, first_level, t->levels);
+    p.n = ml.n;
+    for (int32_t j = 0; j < ml.n; j++) {
+        p.sh[j] = 2u * (uint32_t)(kCeilK0 + ml.level[j]);
+        p.off[j] = t->ceil_off[ml.level[j]];
+    }
+    return p;
+}
+
 CeilFineSpan ceil_fine_span(const svo_tree* t, const std::pair<int64_t, int64_t>& level0_rows) {
     const int64_t w = (int64_t)1 << (2 * t->levels - kCeilFineSh);  // fine blocks per row
     const int64_t per = (int64_t)1 << (2 * kCeilK0 - kCeilFineSh);  // fine rows per level-0 row

@@ -60,6 +60,24 @@ struct CeilFineSpan {
 // whether a launch whose first ceiling level is `first_level` of the table, with `launch_levels` levels in use, marches on
 // the fine ceilings: they lie one level below the table's finest, so only a launch that starts there descends onto them
 bool ceil_fine_for(int32_t launch_levels, int32_t first_level);
+// The levels of the table coarser than a launch's first level that its march walks before it (CastParams::march_sh,
+// svo_ceil_march.h), coarsest first: levels first_level + 1 .. first_level + kMarchCoarseMax of the `ceil_levels` the table
+// has, each 4 times as wide as the next, and only levels with at least 2 x 2 blocks in a tree of `levels` levels (a single
+// block says nothing a wrap does not repeat).  None (n 0) for a table that does not reach the launch's first level.
+constexpr int32_t kMarchCoarseMax = 2;  // 64- and 256-column blocks above a first level of 16
+struct MarchLevels {
+    int32_t n;
+    int32_t level[kMarchCoarseMax];  // levels of the table
+};
+MarchLevels march_levels(int32_t ceil_levels, int32_t first_level, int32_t levels);
+// ... as a launch takes them over tree t (CastParams::march_n, march_sh, march_off): log2 of each level's block width and its
+// first element in the tree's table (svo_tree.ceil_off); none for a launch that uses no level of it (launch_levels 0)
+struct MarchParams {
+    int32_t n;
+    uint32_t sh[kMarchCoarseMax];
+    int64_t off[kMarchCoarseMax];
+};
+MarchParams march_params(const svo_tree* t, int32_t launch_levels, int32_t first_level);
 CeilFineSpan ceil_fine_span(const svo_tree* t, const std::pair<int64_t, int64_t>& level0_rows);
 
 // the tree's rewritten records (svo_tree.dirty_nodes, sorted here) as runs [first, last] of consecutive indices

@@ -22,6 +22,7 @@ struct Stats {
     uint32_t bends;                                // reflections and refractions (shading)
     uint32_t tints, tint_iters;                    // refractive voxels passed; iterations that ended passing one
     uint32_t march_fine, march_descents;           // the march before the loop: 4-column blocks passed; descents onto them
+    uint32_t march_64, march_256;                  // ... and the blocks passed at its 64- and 256-column levels
 };
 
 // true on one lane of the active lanes (wave-level counters)
@@ -73,11 +74,13 @@ enum : int32_t {
     S_TINTS,
     S_TINT_ITERS = 27,
 };
-// The fine march's counters, after them: a list of their own (MARCH_STAT_NAMES in raytracing_test_amd/__init__.py, in the
+// The march's counters, after them: a list of their own (MARCH_STAT_NAMES in raytracing_test_amd/__init__.py, in the
 // same order), so that the list above and STAT_NAMES stay the 28 slots every earlier reader of the buffer indexes.
 enum : int32_t {
     S_MARCH_FINE = 28,
     S_MARCH_DESCENTS,
+    S_MARCH_64,
+    S_MARCH_256,
 };
-static_assert(S_MARCH_FINE == S_TINT_ITERS + 1 && S_MARCH_DESCENTS + 1 <= SVO_STATS_HEADER,
+static_assert(S_MARCH_FINE == S_TINT_ITERS + 1 && S_MARCH_256 + 1 <= SVO_STATS_HEADER,
               "the counters' slots end before the per-block stamps");

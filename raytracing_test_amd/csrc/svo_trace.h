@@ -571,6 +571,8 @@ __device__ __forceinline__ Hit trace(const CastParams& P, const Mem& mem, const 
         atomicAdd(P.stats + S_TINT_ITERS, (unsigned long long)st.tint_iters);
         atomicAdd(P.stats + S_MARCH_FINE, (unsigned long long)st.march_fine);
         atomicAdd(P.stats + S_MARCH_DESCENTS, (unsigned long long)st.march_descents);
+        atomicAdd(P.stats + S_MARCH_64, (unsigned long long)st.march_64);
+        atomicAdd(P.stats + S_MARCH_256, (unsigned long long)st.march_256);
         // per-ray work (offline analysis, bench.py SVO_RAY_WORK): 16-bit fields, lookups | iterations | brick steps | node loads
         if (ray_work)
             *ray_work = (unsigned long long)min(st.lookups, 65535u) | ((unsigned long long)min(st.iters, 65535u) << 16) |
